@@ -9,8 +9,12 @@ rank 0 and their reassembly.  Scene build / BVH / upload happen once, before
 timing.  N GPUs split the same image (strong scaling): rank r renders row
 blocks b with b % N == r.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--dump-outputs DIR] [--full]
        (N > 1: torchrun --nproc-per-node N bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what takes runs of its
+own: the counted passes, the dominant kernel's roofline, the per-kernel times and the CPU baseline (the line's
+"roofline", "cpu_baseline" and "nan_samples", null without it).
 """
 from __future__ import annotations
 
@@ -55,7 +59,16 @@ def parse():
     ap.add_argument("--spp", type=int, default=0, help="override spp (0 = config's)")
     ap.add_argument("--bvh", default="sah", choices=["sah", "reference"])
     ap.add_argument("--tuning", default="", help='rtw_tuning fields as JSON, e.g. {"wf_iters": 12} (A/B only)')
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the counted passes on the reference and SAH "
+                         "topologies, the dominant kernel's roofline (PMC passes, walk ceiling), the per-kernel "
+                         "HIP-event times and the CPU baseline.  Without it the run sets up, warms up, times the "
+                         "steps and prints the line with those sections null")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, rank 0 saves what the last timed step computed as DIR/<name>.npy "
+                         "(float32): its tile (the frame under --single-process) and the reassembled image; beyond "
+                         "64 MB in all, a fixed seeded sample of each array's pixels")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline duration")
     ap.add_argument("--cpu-threads", type=int, default=8, help="reference uses 8 render threads (main.zig:41)")
     ap.add_argument("--host-backend", action="store_true",
@@ -69,7 +82,10 @@ def parse():
                          "passes of one rank at N, tools/pmc_shard.sh; never a headline number)")
     ap.add_argument("--profiles-dir", default=os.path.join(REPO, "profiles"),
                     help="where the committed PMC passes are read from (tests point it elsewhere)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main():
@@ -139,7 +155,9 @@ def main():
         rccl = {"mode": "single_gpu", "rccl_ranks": None, "backend": None}
     build_s = time.time() - t0
     # the reference topology (bvh.zig) defines the algorithmic bytes
-    world_ref = None if host else pkg.World(pkg.flatten(objs, bvh_mode=pkg._abi.RTW_BVH_REFERENCE), device=local_rank)
+    full = args.full
+    world_ref = (pkg.World(pkg.flatten(objs, bvh_mode=pkg._abi.RTW_BVH_REFERENCE), device=local_rank)
+                 if full and not host else None)
     cam = cfg.camera()
     if args.spp:
         cam.samples_per_pixel = args.spp
@@ -186,14 +204,10 @@ def main():
         torch.cuda.synchronize()
         c = cnt.cpu().numpy()
         return {k: int(c[getattr(pkg._abi, "RTW_STAT_" + k.upper())]) for k in keys}
-    cref = counted(world_ref)
-    cdev = counted(world)
+    cref = counted(world_ref) if full else None
+    cdev = counted(world) if full else None
     if world_ref is not None:
         world_ref.close()
-    nodes, leaves, rays, samples = cref["nodes"], cref["leaves"], cref["rays"], cref["samples"]
-    nan_count = cdev["nan"]
-    pixels = my_rows * W
-    alg_bytes = NODE_BYTES * (nodes + leaves) + 32 * pixels
 
     for _ in range(args.warmup):
         frame_step()
@@ -227,7 +241,10 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t_start
     kernel_ms = host_ms if host else [a.elapsed_time(b) for a, b in ev]
-    if single:  # per-kernel HIP events of device 0's shard, rendered alone after the timed region
+    if args.dump_outputs and rank == 0:  # before anything else renders into the timed path's buffers
+        dump_outputs(args.dump_outputs, frame if single else shard.tile,
+                     None if single or emulated else shard.image)
+    if single and full:  # per-kernel HIP events of device 0's shard, rendered alone after the timed region
         for k in range(args.steps):
             render_step(timing=timings[k])
         torch.cuda.synchronize()
@@ -246,6 +263,85 @@ def main():
             w.close()
     total_samples = (my_rows if emulated else H) * W * spp * args.steps
     value = total_samples / elapsed / 1e6
+    roofline, frac_errors = (derive_roofline(args, pkg, timings, kernel_ms, cref, cdev, my_rows * W, build_id, n_shards,
+                                             shard_rank, single, host) if full else (None, []))
+
+    cpu = None
+    if full and rank == 0 and world_size == 1 and not args.no_cpu_baseline:
+        cpu = cpu_baseline(pkg, arr, cam, args)
+
+    if rank == 0:
+        line = {
+            "metric": ("Msamples/s (pixel·spp) on 1200×800 Book-1 random-spheres @500spp; 1→8 GPU"
+                       if args.config == "c2" else f"Msamples/s (pixel·spp) on {cfg.description}"),
+            "value": round(value, 3),
+            "unit": "Msamples/s",
+            "n_gpus": n_shards,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic: seeded %s scene (%d world objects), counter-based RNG seed 0" % (args.config, len(objs)),
+            "config": {"workload": cfg.description, "config_id": args.config, "width": W, "height": H,
+                       "spp": spp, "max_depth": cam.max_depth, "objects": len(objs), "bvh_nodes": stats["n_nodes"],
+                       "bvh_depth": stats["depth"], "parallelism": f"row-interleaved tiles x{n_shards}"
+                       + ((" + gloo gather (host backend)" if host else " + RCCL gather") if distributed else "")
+                       + (" (one process, rtw_multi: grouped RCCL send/recv)" if single else ""),
+                       "rows_per_block": ROWS_PER_BLOCK, "row_split": "balanced" if ROWS_BALANCED else "blocks",
+                       "exchange": rccl,
+                       "shard": {"n_shards": n_shards, "rank": shard_rank, "rows": my_rows,
+                                 "emulated": emulated},
+                       "timed_scope": ("host contexts (rtw_render_rows) into host tiles, gathered over gloo: the "
+                                       "CPU rehearsal of the torchrun flow" if host else
+                                       "device API (rtw_render_rows_device / rtw_render_multi_device) into an "
+                                       "HBM-resident float4 accumulator; no host copy inside the timed region")},
+            "roofline": roofline,
+            "cpu_baseline": cpu,
+            "nan_samples": cdev["nan"] if full else None,
+            "full": full,
+            "scene_build_s": round(build_s, 4),
+            "build_id": build_id,
+        }
+        print(json.dumps(line), flush=True)
+    world.close()
+    if distributed:
+        dist.destroy_process_group()
+    if frac_errors:
+        print("bench.py: " + "; ".join(frac_errors), file=sys.stderr, flush=True)
+        sys.exit(3)
+
+
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, tile, image):
+    """--dump-outputs (rank 0): what the last timed step left in the timed path's output buffers, as float32 .npy
+    files: `tile` (rank 0's float4 tile as rtw_render_rows_device filled it; the frame of rtw_render_multi_device
+    under --single-process) and `image` (the frame the gather reassembled, if any).  An array beyond its share
+    of DUMP_BYTES is saved as a sample of its pixels (float4 rows), the same sorted seed-0 draw in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"tile": tile}
+    if image is not None:
+        arrays["image"] = image
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().astype(np.float32, copy=False).reshape(-1, 4)
+        keep = (share - 256) // 16  # 256: room for the .npy header
+        if len(a) > keep:
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+def derive_roofline(args, pkg, timings, kernel_ms, cref, cdev, pixels, build_id, n_shards, shard_rank, single, host):
+    """--full: the roofline section of the line, from the timed steps' HIP events (timings, kernel_ms), the counted
+    passes (cref: reference topology, cdev: the device's) and the committed PMC passes; and the errors of any
+    fraction above 1."""
+    nodes, leaves, rays, samples = cref["nodes"], cref["leaves"], cref["rays"], cref["samples"]
+    alg_bytes = NODE_BYTES * (nodes + leaves) + 32 * pixels
     render_s = sum(kernel_ms) / len(kernel_ms) / 1e3          # whole render call (all kernels) per step
     kms = {n: sum(t.ms[i] for t in timings) for i, n in enumerate(pkg._abi.RTW_K_NAMES)}
     kcalls = {n: sum(t.launches[i] for t in timings) for i, n in enumerate(pkg._abi.RTW_K_NAMES)}
@@ -356,52 +452,7 @@ def main():
             sec["error"] = (f"{name} frac {sec['frac']} > 1 from {sec.get('source') or roofline['valu']['source']}: "
                             "a measurement bug")
             frac_errors.append(sec["error"])
-
-    cpu = None
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(pkg, arr, cam, args)
-
-    if rank == 0:
-        line = {
-            "metric": ("Msamples/s (pixel·spp) on 1200×800 Book-1 random-spheres @500spp; 1→8 GPU"
-                       if args.config == "c2" else f"Msamples/s (pixel·spp) on {cfg.description}"),
-            "value": round(value, 3),
-            "unit": "Msamples/s",
-            "n_gpus": n_shards,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic: seeded %s scene (%d world objects), counter-based RNG seed 0" % (args.config, len(objs)),
-            "config": {"workload": cfg.description, "config_id": args.config, "width": W, "height": H,
-                       "spp": spp, "max_depth": cam.max_depth, "objects": len(objs), "bvh_nodes": stats["n_nodes"],
-                       "bvh_depth": stats["depth"], "parallelism": f"row-interleaved tiles x{n_shards}"
-                       + ((" + gloo gather (host backend)" if host else " + RCCL gather") if distributed else "")
-                       + (" (one process, rtw_multi: grouped RCCL send/recv)" if single else ""),
-                       "rows_per_block": ROWS_PER_BLOCK, "row_split": "balanced" if ROWS_BALANCED else "blocks",
-                       "exchange": rccl,
-                       "shard": {"n_shards": n_shards, "rank": shard_rank, "rows": my_rows,
-                                 "emulated": emulated},
-                       "timed_scope": ("host contexts (rtw_render_rows) into host tiles, gathered over gloo: the "
-                                       "CPU rehearsal of the torchrun flow" if host else
-                                       "device API (rtw_render_rows_device / rtw_render_multi_device) into an "
-                                       "HBM-resident float4 accumulator; no host copy inside the timed region")},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "nan_samples": nan_count,
-            "scene_build_s": round(build_s, 4),
-            "build_id": build_id,
-        }
-        print(json.dumps(line), flush=True)
-    world.close()
-    if distributed:
-        dist.destroy_process_group()
-    if frac_errors:
-        print("bench.py: " + "; ".join(frac_errors), file=sys.stderr, flush=True)
-        sys.exit(3)
+    return roofline, frac_errors
 
 
 def pmc_build_id(data):

@@ -206,7 +206,7 @@ def test_bench_torchrun_line_never_carries_a_whole_frame_roofline(tmp_path, worl
     rn = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world_size}",
                          "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
                          "--gpus", str(world_size), "--host-backend", "--config", "c1", "--steps", "1", "--warmup", "0",
-                         "--no-cpu-baseline", "--profiles-dir", str(tmp_path)],
+                         "--full", "--no-cpu-baseline", "--profiles-dir", str(tmp_path)],
                         capture_output=True, text=True, timeout=300, cwd=REPO, env=env)
     assert rn.returncode == 0, rn.stderr[-2000:]
     d = json.loads([ln for ln in rn.stdout.splitlines() if ln.startswith("{")][-1])
@@ -217,6 +217,48 @@ def test_bench_torchrun_line_never_carries_a_whole_frame_roofline(tmp_path, worl
     assert r["valu"]["lane_ops_per_launch"] is None and r["traffic"] is None
     assert "no pass of this rank's shard" in r["valu"]["source"]
     assert "no pass of this rank's shard" in r["hbm"]["source"]
+
+
+def test_plain_run_dumps_the_timed_outputs(tmp_path):
+    """A plain bench.py run (--host-backend: no GPU) leaves the --full sections null, times --steps steps, and
+    --dump-outputs saves the last timed step's tile and reassembled image as float32 .npy, the image equal to
+    --dump-image's frame."""
+    import numpy as np
+    env = dict(os.environ)
+    env.pop("RTW_LIB", None)
+    out = tmp_path / "out"
+    rn = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--host-backend", "--config",
+                         "c1", "--spp", "2", "--steps", "2", "--warmup", "0", "--dump-outputs", str(out),
+                         "--dump-image", str(tmp_path / "frame.npy")],
+                        capture_output=True, text=True, timeout=300, cwd=REPO, env=env)
+    assert rn.returncode == 0, rn.stderr[-2000:]
+    d = json.loads([ln for ln in rn.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["full"] is False and d["roofline"] is None and d["cpu_baseline"] is None and d["nan_samples"] is None
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "Msamples/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 400 * 225 * 2 / (d["ms_per_step"] / 1e3) / 1e6) <= 0.01 * d["value"]
+    assert sorted(os.listdir(out)) == ["image.npy", "tile.npy"]
+    tile, image = np.load(out / "tile.npy"), np.load(out / "image.npy")
+    assert tile.dtype == np.float32 and image.dtype == np.float32
+    assert image.shape == (400 * 225, 4) and (image[:, 3] == 2).all() and len(tile) >= len(image)
+    assert np.array_equal(image, np.load(tmp_path / "frame.npy").reshape(-1, 4))
+
+
+def test_dump_outputs_samples_a_large_array(tmp_path, monkeypatch):
+    """Beyond the size limit dump_outputs keeps the same seeded sample of each array's pixels in every run."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 16 * 1000)
+    a = torch.arange(4 * 3000, dtype=torch.float32).reshape(-1, 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), a, a.reshape(30, 100, 4))
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("tile", "image")}
+    for n, g in got.items():
+        assert g.dtype == np.float32 and g.shape == (484, 4)
+        assert np.array_equal(g, np.load(tmp_path / "b" / f"{n}.npy"))
+        idx = (g[:, 0] / 4).astype(int)
+        assert (np.diff(idx) > 0).all() and np.array_equal(g, a.numpy()[idx])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 16 * 1000
 
 
 def test_prof_summary_keeps_only_the_timed_region(tmp_path):

@@ -14,7 +14,7 @@ done
 for r in $(seq $ROUNDS); do
   for lib in "$@"; do
     tag=$(basename "${lib:-default}" .so)
-    RTW_LIB=$lib timeout -k 10 400 python bench.py --config $CONFIG --no-cpu-baseline --steps $STEPS --warmup 1 \
+    RTW_LIB=$lib timeout -k 10 400 python bench.py --full --config $CONFIG --no-cpu-baseline --steps $STEPS --warmup 1 \
       > "$OUT/${CONFIG}_${tag}_$r.json" 2> "$OUT/ab.err" || { echo "bench $lib failed"; tail -5 "$OUT/ab.err"; exit 1; }
     python3 -c "import json;d=json.load(open('$OUT/${CONFIG}_${tag}_$r.json'));print('$CONFIG', '$tag', $r, d['value'], d['roofline']['kernel_ms_per_step'])"
   done

@@ -21,7 +21,7 @@ for r in $(seq $ROUNDS); do
   n=0
   for tu in "$@"; do
     n=$((n+1))
-    timeout -k 10 400 python bench.py --config $CONFIG --no-cpu-baseline --steps $STEPS --warmup 1 ${BENCH_EXTRA:-} ${tu:+--tuning "$tu"} \
+    timeout -k 10 400 python bench.py --full --config $CONFIG --no-cpu-baseline --steps $STEPS --warmup 1 ${BENCH_EXTRA:-} ${tu:+--tuning "$tu"} \
       > "$OUT/${CONFIG}_t${n}_$r.json" 2> "$OUT/ab.err" || { echo "bench '$tu' failed"; tail -5 "$OUT/ab.err"; exit 1; }
     python3 -c "import json;d=json.load(open('$OUT/${CONFIG}_t${n}_$r.json'));print('$CONFIG', '''$tu''', $r, d['value'], d['roofline']['kernel_ms_per_step'])"
   done

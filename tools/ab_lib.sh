@@ -11,7 +11,7 @@ for r in $(seq $ROUNDS); do
   for lib in "$@"; do
     k=$((k+1))
     f="$OUT/${CONFIG}_${k}_${r}.json"
-    RTW_LIB=$lib timeout -k 10 300 python bench.py --config $CONFIG --spp $SPP --no-cpu-baseline --steps $STEPS \
+    RTW_LIB=$lib timeout -k 10 300 python bench.py --full --config $CONFIG --spp $SPP --no-cpu-baseline --steps $STEPS \
       --warmup 1 > "$f" 2> "$OUT/ab.err" || { echo "bench $lib failed"; tail -5 "$OUT/ab.err"; exit 1; }
     python3 -c "import json;d=json.load(open('$f'));print('$CONFIG', repr('$lib'), $r, d['value'], d['roofline']['kernel_ms_per_step'])"
   done

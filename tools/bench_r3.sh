@@ -5,12 +5,12 @@ set -u
 OUT=gpurun_out/r3
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 300 python bench.py > "$OUT/c2_bench.json" 2> "$OUT/c2.err" || exit $?
-timeout -k 10 300 python bench.py --config c3 --no-cpu-baseline --steps 1 > "$OUT/c3_bench.json" 2> "$OUT/c3.err" || exit $?
+timeout -k 10 300 python bench.py --full > "$OUT/c2_bench.json" 2> "$OUT/c2.err" || exit $?
+timeout -k 10 300 python bench.py --full --config c3 --no-cpu-baseline --steps 1 > "$OUT/c3_bench.json" 2> "$OUT/c3.err" || exit $?
 for c in c4 c5 cornell cornell_smoke simple_light; do
-  timeout -k 10 300 python bench.py --config $c --no-cpu-baseline --steps 2 > "$OUT/${c}_bench.json" 2> "$OUT/$c.err" || exit $?
+  timeout -k 10 300 python bench.py --full --config $c --no-cpu-baseline --steps 2 > "$OUT/${c}_bench.json" 2> "$OUT/$c.err" || exit $?
 done
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py --no-cpu-baseline --steps 2 --warmup 0 > "$OUT/rocprof.log" 2>&1 || exit $?
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py --full --no-cpu-baseline --steps 2 --warmup 0 > "$OUT/rocprof.log" 2>&1 || exit $?
 grep "^{" "$OUT/rocprof.log" > "$OUT/rocprof_bench.json"
 python tools/prof_summary.py "$OUT"/prof/*/run_kernel_trace.csv --json "$OUT/rocprof_bench.json" > "$OUT/c2_timed_summary.txt" 2>&1 || \
   python tools/prof_summary.py "$OUT"/prof/run_kernel_trace.csv --json "$OUT/rocprof_bench.json" > "$OUT/c2_timed_summary.txt" 2>&1

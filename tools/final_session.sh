@@ -31,12 +31,12 @@ if [ "$PART" = bench ]; then
   RTW_LIB=build/rtw_trav.so timeout -k 10 300 python diag/run_walk_ceiling.py c2 "$O/walk_ceiling_c2.json" > "$O/walk_c2.log" 2>&1 || { tail "$O/walk_c2.log"; exit 1; }
   cat "$O/walk_c2.log" | grep '^{'
   cp "$O/walk_ceiling_c2.json" profiles/walk_ceiling_c2.json || exit 1
-  timeout -k 10 300 python bench.py > "$O/c2_bench.json" 2> "$O/c2.err" || { tail "$O/c2.err"; exit 1; }
-  timeout -k 10 300 python bench.py --config c3 --no-cpu-baseline --steps 1 > "$O/c3_bench.json" 2> "$O/c3.err" || { tail "$O/c3.err"; exit 1; }
+  timeout -k 10 300 python bench.py --full > "$O/c2_bench.json" 2> "$O/c2.err" || { tail "$O/c2.err"; exit 1; }
+  timeout -k 10 300 python bench.py --full --config c3 --no-cpu-baseline --steps 1 > "$O/c3_bench.json" 2> "$O/c3.err" || { tail "$O/c3.err"; exit 1; }
   for c in c4 c5 cornell cornell_smoke simple_light; do
-    timeout -k 10 300 python bench.py --config $c --no-cpu-baseline --steps 2 > "$O/${c}_bench.json" 2> "$O/$c.err" || { tail "$O/$c.err"; exit 1; }
+    timeout -k 10 300 python bench.py --full --config $c --no-cpu-baseline --steps 2 > "$O/${c}_bench.json" 2> "$O/$c.err" || { tail "$O/$c.err"; exit 1; }
   done
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- python bench.py --no-cpu-baseline --steps 2 --warmup 0 > "$O/rocprof.log" 2>&1 || { tail "$O/rocprof.log"; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- python bench.py --full --no-cpu-baseline --steps 2 --warmup 0 > "$O/rocprof.log" 2>&1 || { tail "$O/rocprof.log"; exit 1; }
   grep "^{" "$O/rocprof.log" > "$O/rocprof_bench.json"
   python tools/prof_summary.py "$O"/prof/*/run_kernel_trace.csv --json "$O/rocprof_bench.json" > "$O/c2_timed_summary.txt" 2>&1 || \
     python tools/prof_summary.py "$O"/prof/run_kernel_trace.csv --json "$O/rocprof_bench.json" > "$O/c2_timed_summary.txt" 2>&1

@@ -19,9 +19,9 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ -n "${TUNE_ARGS:-}" ]; then step tune 600 python tools/tune.py ${TUNE_ARGS}; fi
-step bench 900 python bench.py ${BENCH_ARGS:-}
+step bench 900 python bench.py --full ${BENCH_ARGS:-}
 if [ "${PROFILE:-1}" = 1 ]; then
-  step rocprof 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py --no-cpu-baseline --steps 2 --warmup 0 ${BENCH_ARGS:-}
+  step rocprof 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py --full --no-cpu-baseline --steps 2 --warmup 0 ${BENCH_ARGS:-}
   grep "^{" "$OUT/rocprof.log" > "$OUT/rocprof_bench.json" || true
   python tools/prof_summary.py "$OUT/prof/run_kernel_trace.csv" --json "$OUT/rocprof_bench.json" > "$OUT/prof_timed_summary.txt" 2>&1 || true
   cat "$OUT/prof_timed_summary.txt"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Stall breakdown of the bench's kernels per launch: SQ counter groups, one
 # rocprofv3 --pmc pass each (<= 8 SQ counters per pass, kernel-trace only), over
-# `bench.py --steps 1 --warmup 0` of $BENCH_ARGS.  Summary: tools/pmc_stall_summary.py.
+# `bench.py --full --steps 1 --warmup 0` of $BENCH_ARGS.  Summary: tools/pmc_stall_summary.py.
 set -u
 OUT=${OUT:-gpurun_out/pmc_stall}
 mkdir -p "$OUT"
@@ -17,7 +17,7 @@ for grp in "${GROUPS_PMC_1-$G1}" "${GROUPS_PMC_2-$G2}" "${GROUPS_PMC_3-$G3}" "${
   i=$((i + 1))
   [ -n "$grp" ] || continue
   echo "== g$i: $grp"
-  timeout -s KILL 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d "$OUT/g$i" -o pmc -- python bench.py $ARGS > "$OUT/g$i.log" 2>&1
+  timeout -s KILL 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d "$OUT/g$i" -o pmc -- python bench.py --full $ARGS > "$OUT/g$i.log" 2>&1
   rc=$?
   echo "   rc=$rc"; tail -n 2 "$OUT/g$i.log" | cut -c1-300
   # 1 = rocprofv3 refused the counter set (unknown counter): next group; anything else stops

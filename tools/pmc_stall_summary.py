@@ -1,6 +1,6 @@
 """Per-launch stall breakdown of the bench's kernels from tools/pmc_stall.sh output.
 
-Each group g<i>/ is one rocprofv3 --pmc pass over `bench.py --steps 1 --warmup 0`; as in
+Each group g<i>/ is one rocprofv3 --pmc pass over `bench.py --full --steps 1 --warmup 0`; as in
 tools/pmc_summary.py the LAST n launches of each kernel kind are the timed step's (n from the bench
 line in g<i>.log).  Counters of the same (kind, launch) are merged across passes.
 

@@ -5,7 +5,7 @@ L2's memory-side request counters (Infinity-Cache hits included).  gfx950
 correction: FETCH_SIZE reports 1/2 of the bytes of wide coalesced reads, so
 read bytes = 2 x FETCH_SIZE x 1024; WRITE_SIZE is exact for 16-B/lane stores.
 
-The profiled command is `bench.py --steps 1 --warmup 0`: two counted passes
+The profiled command is `bench.py --full --steps 1 --warmup 0`: two counted passes
 precede the timed step.  Kernels are grouped by kind (wf_gen / wf_trace* /
 wf_shade / wf_tail / wf_reduce: variants of a kind share the group) and the
 LAST n launches of each kind are kept, n = that kind's launches per step in the

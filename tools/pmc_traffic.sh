@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 ARGS=${BENCH_ARGS:-"--no-cpu-baseline --steps 1 --warmup 0"}
 for c in FETCH_SIZE WRITE_SIZE; do
   echo "== $c"
-  timeout -k 10 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/$c" -o pmc -- python bench.py $ARGS > "$OUT/$c.log" 2>&1
+  timeout -k 10 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/$c" -o pmc -- python bench.py --full $ARGS > "$OUT/$c.log" 2>&1
   rc=$?
   echo "   rc=$rc"; tail -n 1 "$OUT/$c.log" | cut -c1-200
   case $rc in 0|1) ;; *) echo "stopping"; exit $rc;; esac

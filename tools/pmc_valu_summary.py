@@ -1,6 +1,6 @@
 """Per-launch VALU issue counters of the bench's kernels from tools/pmc_valu.sh output.
 
-The profiled command is `bench.py --steps 1 --warmup 0`; as in tools/pmc_summary.py
+The profiled command is `bench.py --full --steps 1 --warmup 0`; as in tools/pmc_summary.py
 the LAST n launches of each kernel kind are kept (n = that kind's launches per step
 in the bench line of the same run), i.e. the timed step's launches, and averaged.
 

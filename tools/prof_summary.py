@@ -1,7 +1,7 @@
 """Per-kernel duration summary of a rocprofv3 kernel trace, restricted to the
 timed region of bench.py.
 
-bench.py runs counted renders (reference + SAH topology, which may use other
+bench.py --full runs counted renders (reference + SAH topology, which may use other
 kernel instantiations) and `warmup` renders before the timed steps; rocprofv3
 --stats averages over all of them.  With the bench line (--json), this script
 keeps the timed region only: the last steps x launches_per_step calls of the

@@ -6,9 +6,9 @@ set -u
 CFG=${1:-c2}; N=${2:-8}; TU=${3:-}
 OUT=gpurun_out/r5/shard_${CFG}_n${N}${TAG:+_$TAG}
 mkdir -p $OUT
-timeout -k 10 300 python bench.py --config $CFG --no-cpu-baseline --steps 3 --warmup 1 ${TU:+--tuning "$TU"} > $OUT/n1.json 2> $OUT/err || { tail $OUT/err; exit 1; }
+timeout -k 10 300 python bench.py --full --config $CFG --no-cpu-baseline --steps 3 --warmup 1 ${TU:+--tuning "$TU"} > $OUT/n1.json 2> $OUT/err || { tail $OUT/err; exit 1; }
 for r in $(seq 0 $((N-1))); do
-  timeout -k 10 300 python bench.py --config $CFG --shard $N,$r --no-cpu-baseline --steps 3 --warmup 1 ${TU:+--tuning "$TU"} \
+  timeout -k 10 300 python bench.py --full --config $CFG --shard $N,$r --no-cpu-baseline --steps 3 --warmup 1 ${TU:+--tuning "$TU"} \
     > $OUT/r$r.json 2> $OUT/err || { tail $OUT/err; exit 1; }
 done
 python - "$OUT" "$N" <<'PY'
