@@ -147,6 +147,10 @@ typedef struct rtw_transform {
 #define RTW_MAX_XF 3
 enum { RTW_INST_LIST = 1u };   /* rtw_instance.flags: the members form a HittableList (its box
                                   starts from the zero Aabb{}, objects.zig:264-279); else one primitive */
+enum { RTW_INST_BVH = 2u };    /* rtw_instance.flags: the library builds a private BVH over the members in object
+                                  space (a Hittable{.tree} under the transforms) and walks it instead of testing
+                                  them one after another.  Same box, same closest hit as the list.  Instances of
+                                  more than 127 members get one whether flagged or not. */
 /* A HittableList (createBox, src/objects.zig:264-290, 510-532) of members[first ..
  * first + count) -- spheres or quads -- wrapped in xf[0] (innermost) .. xf[n_xf-1]
  * (outermost), e.g. Translate(RotateY(createBox(...))) = {ROTATE_Y, TRANSLATE}.  64 bytes. */
@@ -528,6 +532,12 @@ typedef struct rtw_scene_stats {
 int rtw_scene_stats_get(rtw_ctx* ctx, rtw_scene_stats* out);
 /* Copies the flattened node array (32 B per node) to host. */
 int rtw_scene_nodes(rtw_ctx* ctx, void* out, uint32_t cap, uint32_t* n_out);
+/* Copies the private BVH of instance `instance` (RTW_INST_BVH, or more than 127 members): 32 B per node, the
+ * same pre-order / skip-link layout in the instance's object space, sized like rtw_scene_nodes (out may be
+ * NULL to query the count).  Leaves: b.y = bits(member index within the instance), b.z = bits(sphere / quad
+ * index), b.w = bits(moving | kind << 8); sphere leaves carry (center1, radius) in a.xyz / b.x.
+ * *n_out = 0 for an instance without a tree.  Works on host contexts. */
+int rtw_scene_instance_nodes(rtw_ctx* ctx, uint32_t instance, void* out, uint32_t cap, uint32_t* n_out);
 
 /* Debug / known-answer hooks, executed ON THE DEVICE by the same device
  * functions the render kernel uses. */

@@ -51,6 +51,8 @@ OBJECT_DT = np.dtype([("kind", "<u4"), ("index", "<u4")])
 XF_DT = np.dtype([("kind", "<u4"), ("v", "<f4", 3)])
 RTW_MAX_XF = 3
 RTW_INST_LIST = 1
+RTW_INST_BVH = 2            # the library builds a private BVH over the members (always above 127)
+RTW_INST_LIST_MAX = 127
 INSTANCE_DT = np.dtype([("first", "<u4"), ("count", "<u4"), ("n_xf", "<u4"), ("flags", "<u4"),
                         ("xf", XF_DT, RTW_MAX_XF)])
 MEDIUM_DT = np.dtype([("boundary", OBJECT_DT), ("density", "<f4"), ("material", "<u4")])
@@ -210,6 +212,7 @@ SIGNATURES = {
                                     C.POINTER(C.c_uint32)]),
     "rtw_scene_stats_get": (C.c_int, [C.c_void_p, C.POINTER(RtwSceneStats)]),
     "rtw_scene_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "rtw_scene_instance_nodes": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rtw_debug_rng": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "rtw_debug_sample": (C.c_int, [C.c_void_p, C.POINTER(RtwCamera), C.c_uint64, C.c_uint32, C.c_uint32,
                                    C.c_void_p]),

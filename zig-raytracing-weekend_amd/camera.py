@@ -265,3 +265,9 @@ def cornell_smoke_camera(image_width: int = 600, spp: int = 200, max_depth: int 
     """cornellBoxSmoke's camera (src/main.zig:238-246)."""
     return cornell_camera(image_width, spp, max_depth)
 
+
+def next_week_camera(image_width: int = 800, spp: int = 10000, max_depth: int = 40) -> Camera:
+    """The camera of the *Next Week* final scene (worlds.next_week_world): square, black background."""
+    return Camera(aspect_ratio=1.0, image_width=image_width, samples_per_pixel=spp, max_depth=max_depth, vfov=40.0,
+                  lookfrom=(478.0, 278.0, -600.0), lookat=(278.0, 278.0, 0.0), vup=(0.0, 1.0, 0.0),
+                  defocus_angle=0.0)

@@ -5,7 +5,7 @@ from dataclasses import dataclass
 from typing import Callable, List
 
 from . import worlds
-from .camera import Camera, book1_camera, cornell_camera, cornell_smoke_camera, earth_perlin_camera, simple_light_camera
+from .camera import Camera, book1_camera, cornell_camera, cornell_smoke_camera, earth_perlin_camera, next_week_camera, simple_light_camera
 from .scene import Sphere
 
 
@@ -41,4 +41,8 @@ CONFIGS = {
                             worlds.cornell_smoke, lambda: cornell_smoke_camera(600, 200, 50)),
     "simple_light": Config("simple_light", "Perlin spheres + quad/sphere lights 800x450, 100 spp, depth 50",
                            lambda: worlds.simple_light_world(0), lambda: simple_light_camera(800, 100)),
+    # the Next Week final scene: 400 ground boxes, media, textures and the 1000-sphere cluster as one instance
+    # walked through its own BVH (not a bench.py choice)
+    "next_week": Config("next_week", "Next Week final scene 800x800, 64 spp, depth 40 (1000-sphere tree instance)",
+                        lambda: worlds.next_week_world(0), lambda: next_week_camera(800, 64, 40)),
 }

@@ -159,8 +159,9 @@ public:
         itrue_.resize(d.n_instances);
         for (uint32_t i = 0; i < d.n_instances; i++) {
             const rtw_instance& in = d.instances[i];
-            if (in.count == 0 || in.count > 127 || in.first > d.n_members || in.count > d.n_members - in.first ||
-                in.n_xf > RTW_MAX_XF)
+            // (more than RTW_INST_LIST_MAX members: a tree below; what the hit id allows is checked by
+            // rtw_scene_create_ex, which knows the world tree's size)
+            if (in.count == 0 || in.first > d.n_members || in.count > d.n_members - in.first || in.n_xf > RTW_MAX_XF)
                 return RTW_E_INVALID;
             rtw_dev_instance& o = g_.insts[i];
             o.first = in.first;
@@ -206,6 +207,10 @@ public:
             }
             ibox_[i] = b;
             itrue_[i] = tb;
+            if ((in.flags & RTW_INST_BVH) || in.count > RTW_INST_LIST_MAX) {
+                build_inst_tree(i, in);
+                g_.feat |= RTW_F_TREE;
+            }
         }
         if (d.n_instances) g_.feat |= RTW_F_GEOM;
         // media: ConstantMedium (objects.zig:445-464)
@@ -275,6 +280,114 @@ public:
     }
 
 private:
+    // The private tree of instance i (RTW_INST_BVH, or more members than a list's hit id holds): binned SAH
+    // over the members' TRUE object-space boxes (a moving sphere's spans both centres; a skewed quad's all
+    // four corners, which its reference box can miss), one member per leaf, appended to g_.inodes in the
+    // world tree's pre-order / skip-link layout with indices relative to the instance's root.  Boxes are
+    // unpadded here; rtw_build_bvh pads them (pad_inst_trees).
+    void build_inst_tree(uint32_t i, const rtw_instance& in) {
+        const uint32_t n = in.count;
+        std::vector<Box> bx(n);
+        std::vector<std::array<float, 3>> cent(n);
+        std::vector<uint32_t> idx(n);
+        for (uint32_t m = 0; m < n; m++) {
+            bx[m] = member_true_box(d_.members[in.first + m]);
+            for (int k = 0; k < 3; k++) cent[m][k] = 0.5f * (bx[m].mn[k] + bx[m].mx[k]);
+            idx[m] = m;
+        }
+        const uint32_t base = (uint32_t)g_.inodes.size();
+        g_.insts[i].tree = base + 1u;
+        g_.inodes.reserve(base + 2 * (size_t)n);
+        emit_inst(in, bx, cent, idx, 0, n, base);
+    }
+    static float box_area(const Box& b) {
+        const float dx = b.mx[0] - b.mn[0], dy = b.mx[1] - b.mn[1], dz = b.mx[2] - b.mn[2];
+        return 2.0f * (dx * dy + dy * dz + dz * dx);
+    }
+    Box emit_inst(const rtw_instance& in, const std::vector<Box>& bx, const std::vector<std::array<float, 3>>& cent,
+                  std::vector<uint32_t>& idx, uint32_t a, uint32_t b, uint32_t base) {
+        if (b - a == 1) {
+            const uint32_t m = idx[a];
+            const rtw_object& ref = d_.members[in.first + m];
+            rtw_node n{};
+            const uint32_t w = ((uint32_t)g_.inodes.size() + 1u - base) | RTW_LEAF_BIT;
+            std::memcpy(&n.a[3], &w, 4);
+            uint32_t bw = ref.kind << 8;
+            if (ref.kind == RTW_OBJ_SPHERE) {  // the sphere inline, as a world leaf (no second dependent load)
+                const rtw_sphere& sp = d_.spheres[ref.index];
+                for (int k = 0; k < 3; k++) n.a[k] = sp.center1[k];
+                n.b[0] = sp.radius;
+                bw = sp.is_moving ? 1u : 0u;
+            }
+            std::memcpy(&n.b[1], &m, 4);
+            std::memcpy(&n.b[2], &ref.index, 4);
+            std::memcpy(&n.b[3], &bw, 4);
+            g_.inodes.push_back(n);
+            return bx[m];
+        }
+        const size_t me = g_.inodes.size();
+        g_.inodes.push_back(rtw_node{});
+        // binned SAH over the centroids: the split minimising area x count summed over the two sides
+        float cmn[3], cmx[3];
+        for (int k = 0; k < 3; k++) { cmn[k] = cent[idx[a]][k]; cmx[k] = cmn[k]; }
+        for (uint32_t j = a + 1; j < b; j++)
+            for (int k = 0; k < 3; k++) {
+                cmn[k] = std::min(cmn[k], cent[idx[j]][k]);
+                cmx[k] = std::max(cmx[k], cent[idx[j]][k]);
+            }
+        constexpr int NB = 16;
+        auto bin_of = [&](uint32_t o, int ax) {
+            int bin = (int)((cent[o][ax] - cmn[ax]) / (cmx[ax] - cmn[ax]) * NB);
+            return bin < 0 ? 0 : (bin >= NB ? NB - 1 : bin);
+        };
+        float best = __builtin_inff();
+        int best_axis = -1, best_bin = 0;
+        for (int ax = 0; ax < 3; ax++) {
+            if (!(cmx[ax] - cmn[ax] > 0)) continue;
+            Box bb[NB];
+            uint32_t cnt[NB] = {0};
+            for (uint32_t j = a; j < b; j++) {
+                const int bin = bin_of(idx[j], ax);
+                bb[bin] = cnt[bin] ? box_union(bb[bin], bx[idx[j]]) : bx[idx[j]];
+                cnt[bin]++;
+            }
+            float rarea[NB];
+            uint32_t rcnt[NB];
+            Box acc{};
+            uint32_t c = 0;
+            for (int k = NB - 1; k > 0; k--) {
+                if (cnt[k]) acc = c ? box_union(acc, bb[k]) : bb[k];
+                c += cnt[k];
+                rarea[k] = c ? box_area(acc) : 0.0f;
+                rcnt[k] = c;
+            }
+            c = 0;
+            for (int k = 0; k < NB - 1; k++) {
+                if (cnt[k]) acc = c ? box_union(acc, bb[k]) : bb[k];
+                c += cnt[k];
+                if (c == 0 || rcnt[k + 1] == 0) continue;
+                const float cost = box_area(acc) * (float)c + rarea[k + 1] * (float)rcnt[k + 1];
+                if (cost < best) { best = cost; best_axis = ax; best_bin = k; }
+            }
+        }
+        uint32_t mid = a + (b - a) / 2;  // coinciding centroids: halves, in member order
+        if (best_axis >= 0) {
+            auto it = std::stable_partition(idx.begin() + a, idx.begin() + b,
+                                            [&](uint32_t o) { return bin_of(o, best_axis) <= best_bin; });
+            const uint32_t p = (uint32_t)(it - idx.begin());
+            if (p > a && p < b) mid = p;
+        }
+        const Box lb = emit_inst(in, bx, cent, idx, a, mid, base);
+        const Box rb = emit_inst(in, bx, cent, idx, mid, b, base);
+        const Box box = box_union(lb, rb);
+        rtw_node& o = g_.inodes[me];
+        const uint32_t skip = (uint32_t)g_.inodes.size() - base;
+        for (int k = 0; k < 3; k++) { o.a[k] = box.mn[k]; o.b[k] = box.mx[k]; }
+        std::memcpy(&o.a[3], &skip, 4);
+        o.b[3] = 0.0f;
+        return box;
+    }
+
     Box member_box(const rtw_object& m) const { return m.kind == RTW_OBJ_SPHERE ? sbox_[m.index] : qbox_[m.index]; }
     Box member_true_box(const rtw_object& m) const { return m.kind == RTW_OBJ_SPHERE ? sbox_[m.index] : qtrue_[m.index]; }
     Box object_box(const rtw_object& r) const {
@@ -665,6 +778,48 @@ private:
 
 }  // namespace
 
+namespace {
+// Pads the inner boxes of every instance tree so that both slab tests of inst_tree_t only ever cull boxes no
+// member test could accept a hit in.  The world walk's pad is E * 2^-19 for origins with |o| <= 7E (below);
+// an instance tree is walked in OBJECT space, where the origin is the world origin taken through the inverse
+// transforms: with world origins within 7 * e_world (what the fast slab test admits), a translation adds at
+// most its largest component and a rotation about y at most a factor sqrt(2).  E_i = max(the tree's own
+// extent, that bound / 7), and the pad is E_i * 2^-17: four times the world walk's margin, since the hit a
+// member test accepts is a point computed through the transform chain, not the exact intersection.  The root
+// keeps reach = 7 * E_i in b.w: inst_tree_t sends origins beyond it (far cameras, which the world walk
+// handles with the exact test) to the member loop, which needs no boxes.
+void pad_inst_trees(rtw_geometry& geom, float e_world) {
+    for (rtw_dev_instance& in : geom.insts) {
+        if (!in.tree || in.count < 2) continue;
+        rtw_node* t = geom.inodes.data() + (in.tree - 1u);
+        float e = 0;
+        for (int k = 0; k < 3; k++) e = std::max(e, std::max(std::fabs(t[0].a[k]), std::fabs(t[0].b[k])));
+        float reach = 7.0f * e_world;
+        for (int k = (int)in.n_xf - 1; k >= 0; k--) {  // outermost first, as inst_to_object
+            uint32_t kind;
+            std::memcpy(&kind, &in.xf[k][0], 4);
+            if (kind == RTW_XF_TRANSLATE)
+                reach += std::max(std::fabs(in.xf[k][1]), std::max(std::fabs(in.xf[k][2]), std::fabs(in.xf[k][3])));
+            else
+                reach *= 1.4142137f;
+        }
+        const float ei = std::max(e, reach / 7.0f);
+        const float pad = ei * 7.6293945e-06f;  // 2^-17
+        const uint32_t n = 2u * in.count - 1u;
+        for (uint32_t j = 0; j < n; j++) {
+            uint32_t w;
+            std::memcpy(&w, &t[j].a[3], 4);
+            if (w & RTW_LEAF_BIT) continue;
+            for (int k = 0; k < 3; k++) {
+                t[j].a[k] -= pad;
+                t[j].b[k] += pad;
+            }
+        }
+        t[0].b[3] = 7.0f * ei;
+    }
+}
+}  // namespace
+
 int rtw_build_bvh(const rtw_scene_desc& desc, std::vector<rtw_node>& nodes, rtw_geometry& geom,
                   uint32_t* depth, uint32_t* axis_draws, float* box_pad, float* extent, uint32_t orders,
                   uint32_t sah_max_leaf, uint32_t hoist, uint32_t* n_hoisted, uint32_t flatten_pct) {
@@ -722,6 +877,7 @@ int rtw_build_bvh(const rtw_scene_desc& desc, std::vector<rtw_node>& nodes, rtw_
                 geom.insts[i].box[1][k] = b.mx[k] + ipad;
             }
         }
+        pad_inst_trees(geom, e);
         if (box_pad) *box_pad = pad;
         if (extent) *extent = e;
         return RTW_OK;
@@ -729,6 +885,12 @@ int rtw_build_bvh(const rtw_scene_desc& desc, std::vector<rtw_node>& nodes, rtw_
     if (desc.bvh_mode != RTW_BVH_REFERENCE) return RTW_E_INVALID;
     RefBuilder b(desc, geo, nodes);
     b.build();
+    if (geom.feat & RTW_F_TREE) {  // the same E as the SAH branch: every object's box
+        float e = 0;
+        for (const Obj& o : geo.objects())
+            for (int k = 0; k < 3; k++) e = std::max(e, std::max(std::fabs(o.box.mn[k]), std::fabs(o.box.mx[k])));
+        pad_inst_trees(geom, e);
+    }
     if (depth) *depth = b.depth();
     if (axis_draws) *axis_draws = b.axis_draws();
     return RTW_OK;

@@ -564,6 +564,119 @@ RTW_DHD bool list_t(const rtw_launch& L, const rtw_dev_instance* __restrict__ in
     return any;
 }
 
+RTW_DHD void load_node(const float4* __restrict__ nodes, uint32_t i, float4& A, float4& B);
+
+// HittableList.hit through the instance's own tree (RTW_F_TREE scenes; rtw_bvh.hip InstTreeBuilder): list_t's
+// contract -- an object-space ray, any (tmin, tmax), t and the member index out -- and list_t's result.
+//  * A stackless skip-link walk of 32-B nodes read through L1/L2 (hit -> i + 1, miss -> skip): no stack
+//    registers.  The object-space reciprocals are computed once per visit.  Lanes of the wave outside the
+//    instance idle meanwhile, as in list_t's member loop.
+//  * Boxes only cull: they are the members' true object-space boxes padded by the host for origins with
+//    |o| <= reach (the root's b.w), so both slab tests -- the clamped-reciprocal FMA form of box_next with
+//    L.fast_box, else aabb.zig's arithmetic -- keep every box a member test could accept a hit in.  An origin
+//    beyond reach (a far camera, which also switches the world walk to the exact test) takes list_t.
+//  * Leaves run the list's own tests (sphere_t / quad_t on (tmin, closest), spheres inline in the leaf), so an
+//    accepted t has the list's fp32 value.  Quad.hit accepts t == closest, which in list order lets the later
+//    member win an exact tie (box sides sharing an edge): here a quad at t == closest replaces a quad hit only
+//    when its member index is larger, and always replaces a sphere hit (the list's outcome in either order).
+//    Spheres test the open interval: of spheres with equal roots the first tested wins (unspecified).
+template <uint32_t FEAT>
+RTW_DHD bool inst_tree_t(const rtw_launch& L, const rtw_dev_instance* __restrict__ in, uint32_t tree, const Ray& ro,
+                         float tmin, float tmax, float& t, uint32_t& sub) {
+    const float4* __restrict__ nodes = L.inodes + 2 * (size_t)(tree - 1u);
+    const uint32_t n = 2u * in->count - 1u;
+    {
+        const float4 A0 = nodes[0], B0 = nodes[1];
+        const float om = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(ro.o.x), __builtin_fabsf(ro.o.y)),
+                                         __builtin_fabsf(ro.o.z));
+        if (!(fbits(A0.w) & RTW_LEAF_BIT) && !(om <= B0.w)) return list_t<FEAT>(L, in, ro, tmin, tmax, t, sub);
+    }
+    const bool fast = L.fast_box != 0;
+    f3 inv, oinv = mk(0, 0, 0);
+    if (fast) {  // ray_trav's clamped reciprocals
+        auto ci = [](float d) { return __builtin_fmaxf(__builtin_fminf(RTW_RCP_EST(d), 1e30f), -1e30f); };
+        inv = mk(ci(ro.d.x), ci(ro.d.y), ci(ro.d.z));
+        oinv = mk(-(ro.o.x * inv.x), -(ro.o.y * inv.y), -(ro.o.z * inv.z));
+    } else {
+        inv = mk(RTW_DIV(1.0f, ro.d.x), RTW_DIV(1.0f, ro.d.y), RTW_DIV(1.0f, ro.d.z));
+    }
+    bool any = false, any_quad = false;
+    float closest = tmax;
+    uint32_t i = 0;
+    while (i < n) {
+        float4 A, B;
+        load_node(nodes, i, A, B);
+        const uint32_t w = fbits(A.w);
+        if (w & RTW_LEAF_BIT) {
+            const uint32_t m = fbits(B.y), idx = fbits(B.z), bw = fbits(B.w);
+            float tt;
+            bool h, quad = false;
+            if (RTW_LEAF_KIND(bw) == RTW_OBJ_QUAD) {
+                quad = true;
+                h = quad_t(L.quads[idx], ro, tmin, closest, tt);
+                if (h && any_quad && tt == closest && m < sub) h = false;  // the list's later member keeps the tie
+            } else {
+                f3 c = mk(A.x, A.y, A.z);
+                if constexpr ((FEAT & RTW_F_MOVING) != 0) {
+                    if (bw & 1u) {  // Sphere.getCenter (objects.zig:94-98), as member_sphere_center
+                        const float4 cv = L.cvec[idx];
+                        c = c + splat(ro.time) * mk(cv.x, cv.y, cv.z);
+                    }
+                }
+                h = sphere_t(c, B.x, ro, tmin, closest, tt);
+            }
+            if (h) {
+                closest = tt;
+                sub = m;
+                any = true;
+                any_quad = quad;
+            }
+            i = w & RTW_SKIP_MASK;
+            continue;
+        }
+        float lo, hi;
+        if (fast) {
+            const float t0x = __builtin_fmaf(A.x, inv.x, oinv.x), t1x = __builtin_fmaf(B.x, inv.x, oinv.x);
+            const float t0y = __builtin_fmaf(A.y, inv.y, oinv.y), t1y = __builtin_fmaf(B.y, inv.y, oinv.y);
+            const float t0z = __builtin_fmaf(A.z, inv.z, oinv.z), t1z = __builtin_fmaf(B.z, inv.z, oinv.z);
+            lo = __builtin_fmaxf(__builtin_fmaxf(tmin, __builtin_fminf(t0x, t1x)),
+                                 __builtin_fmaxf(__builtin_fminf(t0y, t1y), __builtin_fminf(t0z, t1z)));
+            hi = __builtin_fminf(__builtin_fminf(closest, __builtin_fmaxf(t0x, t1x)),
+                                 __builtin_fminf(__builtin_fmaxf(t0y, t1y), __builtin_fmaxf(t0z, t1z)));
+        } else {  // aabb.zig:82-114 (box_next's exact form) on [tmin, closest]
+            float t0x = (A.x - ro.o.x) * inv.x, t1x = (B.x - ro.o.x) * inv.x;
+            float t0y = (A.y - ro.o.y) * inv.y, t1y = (B.y - ro.o.y) * inv.y;
+            float t0z = (A.z - ro.o.z) * inv.z, t1z = (B.z - ro.o.z) * inv.z;
+            if (inv.x < 0) { float s = t1x; t1x = t0x; t0x = s; }
+            if (inv.y < 0) { float s = t1y; t1y = t0y; t0y = s; }
+            if (inv.z < 0) { float s = t1z; t1z = t0z; t0z = s; }
+            lo = __builtin_fmaxf(__builtin_fmaxf(tmin, t0x), __builtin_fmaxf(t0y, t0z));
+            hi = __builtin_fminf(__builtin_fminf(closest, t1x), __builtin_fminf(t1y, t1z));
+        }
+        i = (hi < lo) ? w : i + 1;
+    }
+    t = closest;
+    return any;
+}
+
+// HittableList.hit of an instance: its tree where it has one (RTW_F_TREE kernels only), else the member loop
+template <uint32_t FEAT>
+RTW_DHD bool inst_hit_t(const rtw_launch& L, const rtw_dev_instance* __restrict__ in, const Ray& ro, float tmin,
+                        float tmax, float& t, uint32_t& sub) {
+    if constexpr ((FEAT & RTW_F_TREE) != 0) {
+        const uint32_t tree = in->tree;
+        if (tree) return inst_tree_t<FEAT>(L, in, tree, ro, tmin, tmax, t, sub);
+    }
+    return list_t<FEAT>(L, in, ro, tmin, tmax, t, sub);
+}
+
+// the node / member split of a hit id (rtw_layout.h)
+template <uint32_t FEAT>
+RTW_DHD uint32_t hit_node_bits(const rtw_launch& L) {
+    if constexpr ((FEAT & RTW_F_TREE) != 0) return L.hit_bits;
+    return RTW_HIT_NODE_BITS;
+}
+
 // Hittable.hit of a sphere / quad / instance reference (a medium boundary)
 template <uint32_t FEAT>
 RTW_DHD bool boundary_t(const rtw_launch& L, uint32_t ref, const Ray& r, float tmin, float tmax,
@@ -578,7 +691,7 @@ RTW_DHD bool boundary_t(const rtw_launch& L, uint32_t ref, const Ray& r, float t
     default: {
         const rtw_dev_instance* in = L.insts + idx;
         uint32_t sub;
-        return list_t<FEAT>(L, in, inst_to_object(in, r), tmin, tmax, t, sub);
+        return inst_hit_t<FEAT>(L, in, inst_to_object(in, r), tmin, tmax, t, sub);
     }
     }
 }
@@ -594,8 +707,8 @@ RTW_DHD bool medium_t(const rtw_launch& L, uint32_t idx, const Ray& r, float tmi
         const rtw_dev_instance* in = L.insts + RTW_REF_INDEX(m.boundary);
         const Ray ro = inst_to_object(in, r);
         uint32_t sub;
-        if (!list_t<FEAT>(L, in, ro, -kInf, kInf, t1, sub)) return false;  // intervals.universe
-        if (!list_t<FEAT>(L, in, ro, t1 + 0.0001f, kInf, t2, sub)) return false;
+        if (!inst_hit_t<FEAT>(L, in, ro, -kInf, kInf, t1, sub)) return false;  // intervals.universe
+        if (!inst_hit_t<FEAT>(L, in, ro, t1 + 0.0001f, kInf, t2, sub)) return false;
     } else {
         if (!boundary_t<FEAT>(L, m.boundary, r, -kInf, kInf, t1)) return false;  // intervals.universe
         if (!boundary_t<FEAT>(L, m.boundary, r, t1 + 0.0001f, kInf, t2)) return false;
@@ -632,7 +745,7 @@ RTW_DHD bool inst_box_met(const rtw_launch& L, const rtw_dev_instance* __restric
 }
 
 // A non-sphere leaf tested with (0.001, closest): updates closest / hit
-// (hit = node | member << 24 for an instance's list member)
+// (hit = node | member << 24 for an instance's member; << L.hit_bits in RTW_F_TREE kernels)
 template <uint32_t FEAT>
 RTW_DHD void object_leaf(const rtw_launch& L, const Ray& r, const RayTrav& rt, uint32_t kind, uint32_t idx,
                                          uint32_t node, float& closest, int& hit, uint64_t mkey) {
@@ -643,7 +756,7 @@ RTW_DHD void object_leaf(const rtw_launch& L, const Ray& r, const RayTrav& rt, u
         h = quad_t(L.quads[idx], r, kTmin, closest, t);
     } else if (kind == RTW_OBJ_INSTANCE) {
         const rtw_dev_instance* in = L.insts + idx;
-        if (inst_box_met(L, in, rt, closest)) h = list_t<FEAT>(L, in, inst_to_object(in, r), kTmin, closest, t, sub);
+        if (inst_box_met(L, in, rt, closest)) h = inst_hit_t<FEAT>(L, in, inst_to_object(in, r), kTmin, closest, t, sub);
     } else if constexpr ((FEAT & RTW_F_MEDIUM) != 0) {
         const uint32_t b = L.media[idx].boundary;
         if (RTW_REF_KIND(b) != RTW_OBJ_INSTANCE || inst_box_met(L, L.insts + RTW_REF_INDEX(b), rt, closest))
@@ -651,7 +764,7 @@ RTW_DHD void object_leaf(const rtw_launch& L, const Ray& r, const RayTrav& rt, u
     }
     if (h) {
         closest = t;
-        hit = (int)(node | (sub << RTW_HIT_NODE_BITS));
+        hit = (int)(node | (sub << hit_node_bits<FEAT>(L)));
     }
 }
 
@@ -1168,7 +1281,8 @@ RTW_DHD uint32_t hit_material_kind(const float4* __restrict__ nodes, const rtw_l
         nodes = order_base(nodes, L, (uint32_t)hit >> RTW_HIT_NODE_BITS);
         hit &= (1 << RTW_HIT_NODE_BITS) - 1;
     }
-    const uint32_t node = (uint32_t)hit & ((1u << RTW_HIT_NODE_BITS) - 1u);
+    const uint32_t nbits = hit_node_bits<FEAT>(L);
+    const uint32_t node = (uint32_t)hit & ((1u << nbits) - 1u);
     const float4 B = nodes[2 * node + 1];
     uint32_t mat = fbits(B.y);  // sphere leaf
     if constexpr ((FEAT & RTW_F_GEOM) != 0) {
@@ -1176,7 +1290,7 @@ RTW_DHD uint32_t hit_material_kind(const float4* __restrict__ nodes, const rtw_l
         if (kind == RTW_OBJ_QUAD) {
             mat = L.quads[idx].mat;
         } else if (kind == RTW_OBJ_INSTANCE) {
-            const uint32_t ref = L.members[L.insts[idx].first + ((uint32_t)hit >> RTW_HIT_NODE_BITS)];
+            const uint32_t ref = L.members[L.insts[idx].first + ((uint32_t)hit >> nbits)];
             const uint32_t mi = RTW_REF_INDEX(ref);
             mat = RTW_REF_KIND(ref) == RTW_OBJ_SPHERE ? L.sph[mi].mat : L.quads[mi].mat;
         } else if (kind != RTW_OBJ_SPHERE) {
@@ -1194,10 +1308,11 @@ RTW_DHD HitPrep hit_prep(const float4* __restrict__ nodes, const rtw_launch& L, 
         hit &= (1 << RTW_HIT_NODE_BITS) - 1;
     }
     if constexpr ((FEAT & RTW_F_GEOM) != 0) {
-        const uint32_t node = (uint32_t)hit & ((1u << RTW_HIT_NODE_BITS) - 1u);
+        const uint32_t nbits = hit_node_bits<FEAT>(L);
+        const uint32_t node = (uint32_t)hit & ((1u << nbits) - 1u);
         const float4 B = nodes[2 * node + 1];
         const uint32_t kind = RTW_LEAF_KIND(fbits(B.w));
-        if (kind != RTW_OBJ_SPHERE) return object_prep<FEAT>(L, r, kind, fbits(B.z), (uint32_t)hit >> RTW_HIT_NODE_BITS, t);
+        if (kind != RTW_OBJ_SPHERE) return object_prep<FEAT>(L, r, kind, fbits(B.z), (uint32_t)hit >> nbits, t);
     }
     const float4 A = nodes[2 * hit];
     const float4 B = nodes[2 * hit + 1];

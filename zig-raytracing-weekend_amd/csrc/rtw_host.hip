@@ -248,7 +248,29 @@ int rtw_scene_create_ex(const rtw_scene_desc* d, int device, const rtw_tuning* t
         delete ctx;
         return fail(rc, "BVH build failed (bad object graph or bvh_mode)");
     }
-    if ((geom.feat & RTW_F_GEOM) && ctx->nodes_host.size() >= (1u << RTW_HIT_NODE_BITS)) {
+    // The hit id is one 32-bit word, -1 = miss: leaf node | instance member << bits.  Without instance trees
+    // the split is fixed (24 node bits, 7 member bits: lists of at most 127).  With them (RTW_F_TREE) it is
+    // per scene: as many bits as the world tree's nodes need, the rest up to bit 30 for the member.
+    uint32_t hit_bits = RTW_HIT_NODE_BITS;
+    if (geom.feat & RTW_F_TREE) {
+        auto bits = [](uint64_t max_value) {
+            uint32_t b = 1;
+            while (b < 32 && (max_value >> b)) b++;
+            return b;
+        };
+        uint32_t max_count = 1;
+        for (const rtw_dev_instance& in : geom.insts) max_count = std::max(max_count, in.count);
+        const uint32_t nb = bits(ctx->nodes_host.size() - 1), mb = bits(max_count - 1);
+        if (nb + mb > 31) {
+            char msg[200];
+            std::snprintf(msg, sizeof msg,
+                          "hit id limit: %zu BVH nodes (%u bits) and an instance of %u members (%u bits) need more "
+                          "than 31 bits together", ctx->nodes_host.size(), nb, max_count, mb);
+            delete ctx;
+            return fail(RTW_E_INVALID, msg);
+        }
+        hit_bits = nb;
+    } else if ((geom.feat & RTW_F_GEOM) && ctx->nodes_host.size() >= (1u << RTW_HIT_NODE_BITS)) {
         delete ctx;
         return fail(RTW_E_INVALID, "scenes with instances are limited to 2^24 BVH nodes");
     }
@@ -306,6 +328,7 @@ int rtw_scene_create_ex(const rtw_scene_desc* d, int device, const rtw_tuning* t
     const size_t o_cnod = off; off = align(off + cnodes.size() * sizeof(rtw_cnode));
     const size_t o_w2 = off; off = align(off + w2.size() * sizeof(rtw_cnode));
     const size_t o_w2l = off; off = align(off + w2leaf.size() * sizeof(uint32_t));
+    const size_t o_inod = off; off = align(off + geom.inodes.size() * sizeof(rtw_node));  // the instance trees
 
     std::vector<uint8_t> blob(off, 0);
     std::memcpy(blob.data() + o_nodes, ctx->nodes_host.data(), ctx->nodes_host.size() * sizeof(rtw_node));
@@ -315,6 +338,7 @@ int rtw_scene_create_ex(const rtw_scene_desc* d, int device, const rtw_tuning* t
     put(o_cnod, cnodes.data(), cnodes.size() * sizeof(rtw_cnode));
     put(o_w2, w2.data(), w2.size() * sizeof(rtw_cnode));
     put(o_w2l, w2leaf.data(), w2leaf.size() * sizeof(uint32_t));
+    put(o_inod, geom.inodes.data(), geom.inodes.size() * sizeof(rtw_node));
     put(o_cvec, cvec.data(), cvec.size() * sizeof(float));
     put(o_sph, geom.spheres.data(), geom.spheres.size() * sizeof(rtw_dev_sphere));
     put(o_quad, geom.quads.data(), geom.quads.size() * sizeof(rtw_dev_quad));
@@ -393,6 +417,12 @@ int rtw_scene_create_ex(const rtw_scene_desc* d, int device, const rtw_tuning* t
     L.w2nodes = w2.empty() ? nullptr : reinterpret_cast<const uint4*>(dev + o_w2);
     L.w2leaf = w2.empty() ? nullptr : reinterpret_cast<const uint32_t*>(dev + o_w2l);
     L.w2_stack = w2.empty() ? 0u : w2_stack;
+    L.inodes = geom.inodes.empty() ? nullptr : reinterpret_cast<const float4*>(dev + o_inod);
+    L.hit_bits = hit_bits;
+    ctx->inodes_host = geom.inodes;
+    ctx->inst_tree.clear();
+    for (const rtw_dev_instance& in : geom.insts)
+        ctx->inst_tree.emplace_back(in.tree ? in.tree - 1u : 0u, in.tree ? 2u * in.count - 1u : 0u);
     // default cap: 32 candidates for small trees (flat prepass: C2 16/32/64 -> 5765/5789/5769), 128 for large
     // ones (frustum-walked prepass: C4 32/64 -> 2440/2458; round 6, 64/96/128 -> 3147/3156/3166,
     // profiles/r6_late_rest/)
@@ -548,6 +578,15 @@ int rtw_scene_nodes(rtw_ctx* ctx, void* out, uint32_t cap, uint32_t* n_out) {
     const uint32_t n = ctx->stats.n_nodes;  // the first ordering
     if (n_out) *n_out = n;
     if (out) std::memcpy(out, ctx->nodes_host.data(), sizeof(rtw_node) * (cap < n ? cap : n));
+    return RTW_OK;
+}
+
+int rtw_scene_instance_nodes(rtw_ctx* ctx, uint32_t instance, void* out, uint32_t cap, uint32_t* n_out) {
+    if (!ctx) return fail(RTW_E_INVALID, "null ctx");
+    if (instance >= ctx->inst_tree.size()) return fail(RTW_E_INVALID, "instance index out of range");
+    const uint32_t first = ctx->inst_tree[instance].first, n = ctx->inst_tree[instance].second;
+    if (n_out) *n_out = n;
+    if (out && n) std::memcpy(out, ctx->inodes_host.data() + first, sizeof(rtw_node) * (cap < n ? cap : n));
     return RTW_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <condition_variable>
 #include <atomic>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "rtw_layout.h"
@@ -84,6 +85,9 @@ struct rtw_launch {
                                  // in the scene blob) staged in LDS when small; 0 = read through L1/L2
     uint32_t geom_lds;           // node-LDS step/tail: bytes of quads | members | instances (contiguous in the
                                  // scene blob) staged in LDS too; 0 = read through L1/L2
+    // per-instance trees (RTW_F_TREE scenes; rtw_bvh.hip InstTreeBuilder), read through L1/L2
+    const float4* inodes;        // every instance tree's 32-B nodes, one after the other (rtw_dev_instance.tree)
+    uint32_t hit_bits;           // RTW_F_TREE kernels: the hit id is leaf node | member << hit_bits (else 24)
 };
 
 #define RTW_TILE_W 16
@@ -101,6 +105,7 @@ struct rtw_launch {
 #define RTW_F_MEDIUM 64u    // ConstantMedium leaves
 #define RTW_F_SPHERES 31u   // every sphere-scene feature
 #define RTW_F_ALL 127u
+#define RTW_F_TREE 128u     // some instance has a private BVH (inst_tree_t); only ever set on top of RTW_F_ALL
 
 // max nodes staged in LDS by the persistent kernel (48 KiB)
 #define RTW_MEGA_LDS_NODES_MAX 1536
@@ -172,7 +177,8 @@ struct rtw_geometry {
     std::vector<rtw_dev_instance> insts;
     std::vector<uint32_t> members;           // RTW_REF
     std::vector<rtw_dev_medium> media;
-    uint32_t feat = 0;                       // RTW_F_GEOM | RTW_F_MEDIUM as present
+    uint32_t feat = 0;                       // RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_TREE as present
+    std::vector<rtw_node> inodes;            // the instance trees (rtw_dev_instance.tree = first node + 1)
 };
 
 // Validates the object graph, derives the geometry records and builds the BVH
@@ -212,6 +218,8 @@ struct rtw_ctx {
     rtw_launch base{};
     rtw_scene_stats stats{};
     std::vector<rtw_node> nodes_host;
+    std::vector<rtw_node> inodes_host;       // the instance trees, and per instance (first node, node count)
+    std::vector<std::pair<uint32_t, uint32_t>> inst_tree;
     float* d_scratch = nullptr;    // host-API accum staging (rtw_render_ex: the callers' chunks of one frame)
     size_t scratch_bytes = 0;
     float* d_rows = nullptr;       // rtw_render_rows' tile staging (its own: render_ex chunks may be staged

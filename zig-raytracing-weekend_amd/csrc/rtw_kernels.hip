@@ -19,6 +19,7 @@ namespace {
 // samples [s0, s1) looped in order, accumulator read once / written once.
 // Kept as the simple reference kernel (and the A/B baseline for v1).
 // ---------------------------------------------------------------------------
+template <uint32_t FEAT>
 __global__ __launch_bounds__(256) void render_pixels_v0(rtw_launch L) {
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t x = blockIdx.x * 32 + wave * 8 + (lane & 7);
@@ -33,7 +34,7 @@ __global__ __launch_bounds__(256) void render_pixels_v0(rtw_launch L) {
     Counters cnt;
     const uint32_t px = x + L.pixel_offset, py = y + L.pixel_offset;  // camera.zig:100-101
     for (uint32_t s = L.s0; s < L.s1; s++) {
-        f3 c = sample_radiance<RTW_F_ALL>(L.nodes, L, pixel, px, py, s, cnt);
+        f3 c = sample_radiance<FEAT>(L.nodes, L, pixel, px, py, s, cnt);
         if (is_nan3(c)) cnt.nans++;
         acc.x += c.x;
         acc.y += c.y;
@@ -339,12 +340,13 @@ __device__ void debug_filter_check(const rtw_launch& L, const Ray& r, float* out
     }
 }
 
+template <uint32_t FEAT>
 __global__ void debug_sample_kernel(rtw_launch L, uint32_t pixel, uint32_t sample, float* out) {
     if (threadIdx.x | blockIdx.x) return;
     for (int k = 0; k < 32; k++) out[k] = 0;
     Counters cnt;
     const uint32_t x = pixel % L.W, y = pixel / L.W;
-    f3 c = sample_radiance<RTW_F_ALL>(L.nodes, L, pixel, x + L.pixel_offset, y + L.pixel_offset, sample, cnt);
+    f3 c = sample_radiance<FEAT>(L.nodes, L, pixel, x + L.pixel_offset, y + L.pixel_offset, sample, cnt);
     out[0] = c.x;
     out[1] = c.y;
     out[2] = c.z;
@@ -360,7 +362,7 @@ __global__ void debug_sample_kernel(rtw_launch L, uint32_t pixel, uint32_t sampl
     for (uint32_t depth = L.max_depth; depth > 0; depth--, bounce++) {
         debug_filter_check(L, r, out);
         float t;
-        const int hit = traverse<RTW_F_ALL>(L.nodes, L, r, t, cnt, rng.s);
+        const int hit = traverse<FEAT>(L.nodes, L, r, t, cnt, rng.s);
         // brute-force exact closest over all leaves
         {
             const RayTrav rt = ray_trav(r, L.fast_box != 0);
@@ -388,7 +390,7 @@ __global__ void debug_sample_kernel(rtw_launch L, uint32_t pixel, uint32_t sampl
         if (hit < 0) break;
         f3 att;
         Ray sc;
-        if (!shade<RTW_F_ALL>(L.nodes, L, r, hit, t, rng, thr, acc, att, sc)) break;
+        if (!shade<FEAT>(L.nodes, L, r, hit, t, rng, thr, acc, att, sc)) break;
         r = sc;
     }
 }
@@ -410,7 +412,7 @@ int occupancy_v1(size_t lds_bytes) {
 
 uint32_t pick_feat(uint32_t f) {
     if ((f & ~RTW_F_CHECKER) == 0) return f ? RTW_F_CHECKER : 0u;
-    return RTW_F_ALL;
+    return (f & RTW_F_TREE) ? (RTW_F_ALL | RTW_F_TREE) : RTW_F_ALL;  // instance trees: their own instantiation
 }
 
 
@@ -431,7 +433,8 @@ void rtw_launch_render(const rtw_launch& L, void* stream, int variant, int grid)
     if (variant == 0) {
         dim3 block(256);
         dim3 g((L.W + 31) / 32, (L.n_rows + 7) / 8);
-        hipLaunchKernelGGL(render_pixels_v0, g, block, 0, st, L);
+        if (L.feat & RTW_F_TREE) hipLaunchKernelGGL(render_pixels_v0<RTW_F_ALL | RTW_F_TREE>, g, block, 0, st, L);
+        else hipLaunchKernelGGL(render_pixels_v0<RTW_F_ALL>, g, block, 0, st, L);
         return;
     }
     const bool lds = L.n_nodes <= RTW_MEGA_LDS_NODES_MAX && L.use_lds;
@@ -442,6 +445,10 @@ void rtw_launch_render(const rtw_launch& L, void* stream, int variant, int grid)
         break;
     case RTW_F_CHECKER:
         lds ? launch_waves<RTW_F_CHECKER, true>(L, st, grid, w) : launch_waves<RTW_F_CHECKER, false>(L, st, grid, w);
+        break;
+    case RTW_F_ALL | RTW_F_TREE:
+        lds ? launch_waves<RTW_F_ALL | RTW_F_TREE, true>(L, st, grid, w)
+            : launch_waves<RTW_F_ALL | RTW_F_TREE, false>(L, st, grid, w);
         break;
     default:
         lds ? launch_waves<RTW_F_ALL, true>(L, st, grid, w) : launch_waves<RTW_F_ALL, false>(L, st, grid, w);
@@ -462,6 +469,10 @@ int rtw_persistent_grid(uint32_t feat, uint32_t n_nodes, int waves, bool use_lds
     case RTW_F_CHECKER:
         b = lds ? occ_waves<RTW_F_CHECKER, true>(bytes, waves) : occ_waves<RTW_F_CHECKER, false>(bytes, waves);
         break;
+    case RTW_F_ALL | RTW_F_TREE:
+        b = lds ? occ_waves<RTW_F_ALL | RTW_F_TREE, true>(bytes, waves)
+                : occ_waves<RTW_F_ALL | RTW_F_TREE, false>(bytes, waves);
+        break;
     default: b = lds ? occ_waves<RTW_F_ALL, true>(bytes, waves) : occ_waves<RTW_F_ALL, false>(bytes, waves); break;
     }
     return n_cu * b;
@@ -472,5 +483,9 @@ void rtw_launch_debug_rng(uint64_t seed, uint32_t pixel, uint32_t sample, uint32
 }
 
 void rtw_launch_debug_sample(const rtw_launch& L, uint32_t pixel, uint32_t sample, float* d_out, void* stream) {
-    hipLaunchKernelGGL(debug_sample_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, L, pixel, sample, d_out);
+    if (L.feat & RTW_F_TREE)
+        hipLaunchKernelGGL(debug_sample_kernel<RTW_F_ALL | RTW_F_TREE>, dim3(1), dim3(64), 0, (hipStream_t)stream, L, pixel,
+                           sample, d_out);
+    else
+        hipLaunchKernelGGL(debug_sample_kernel<RTW_F_ALL>, dim3(1), dim3(64), 0, (hipStream_t)stream, L, pixel, sample, d_out);
 }

@@ -34,8 +34,11 @@ static_assert(sizeof(rtw_node) == 32, "node must be 32 bytes");
 #define RTW_REF(kind, idx) (((uint32_t)(kind) << 28) | (uint32_t)(idx))
 #define RTW_REF_KIND(r) ((r) >> 28)
 #define RTW_REF_INDEX(r) ((r) & 0x0FFFFFFFu)
-// hit id of a closest hit: leaf node | instance member << 24
+// hit id of a closest hit: leaf node | instance member << 24.  Scenes with instance trees (RTW_F_TREE) split
+// the 31 bits per scene instead: rtw_launch.hit_bits for the world tree's nodes, the rest for the member.
 #define RTW_HIT_NODE_BITS 24
+// members an instance may have without a tree (7 bits of the hit id above the 24 node bits)
+#define RTW_INST_LIST_MAX 127u
 
 // 32 B: every sphere (instance members read these; world-object spheres are inlined in their leaf)
 struct rtw_dev_sphere {
@@ -59,10 +62,13 @@ static_assert(sizeof(rtw_dev_quad) == 80, "quad record must be 80 bytes");
 
 // 96 B: members[first .. first+count) (RTW_REF), xf[k] = {bits(kind), a, b, c}:
 // translate (a, b, c) = offset; rotate_y a = sin, b = cos.  xf[0] innermost.
+// tree: 0 = the members are tested one after another (list_t); else 1 + the index in rtw_launch.inodes of the
+// root of the instance's own tree (2 * count - 1 nodes in object space; leaves: b.y = bits(member index),
+// b.z = bits(sphere / quad index), b.w = bits(moving | kind << 8), spheres inline as in world leaves)
 // box: the instance's world box (RotateY/Translate.init) padded for the leaf's own FMA slab test
 // (rtw_build_bvh; SAH trees only, else +-inf): box[0] = min.xyz, box[1] = max.xyz
 struct rtw_dev_instance {
-    uint32_t first, count, n_xf, _p;
+    uint32_t first, count, n_xf, tree;
     float xf[3][4];
     float box[2][4];
 };

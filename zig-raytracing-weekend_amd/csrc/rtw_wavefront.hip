@@ -2222,6 +2222,7 @@ void wf_run(const rtw_launch& L, const rtw_wf& W0, hipStream_t st, int n_cu, rtw
 #define RTW_F_TEXTURED (RTW_F_CHECKER | RTW_F_IMAGE | RTW_F_NOISE)
 #define RTW_F_MEDIA (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_LIGHT | RTW_F_CHECKER)
 uint32_t wf_pick_feat(uint32_t f) {
+    if (f & RTW_F_TREE) return RTW_F_ALL | RTW_F_TREE;  // instance trees (inst_tree_t): their own instantiation
     if ((f & ~RTW_F_CHECKER) == 0) return f ? RTW_F_CHECKER : 0u;
     if ((f & RTW_F_GEOM) && (f & ~RTW_F_OBJECTS) == 0) return RTW_F_OBJECTS;
     if ((f & ~RTW_F_TEXTURED) == 0) return RTW_F_TEXTURED;
@@ -2247,6 +2248,7 @@ void rtw_wavefront_batch(const rtw_launch& L, const rtw_wf& W, void* stream, int
     case RTW_F_OBJECTS: wf_run<RTW_F_OBJECTS>(L, W, st, n_cu, T); break;
     case RTW_F_TEXTURED: wf_run<RTW_F_TEXTURED>(L, W, st, n_cu, T); break;
     case RTW_F_MEDIA: wf_run<RTW_F_MEDIA>(L, W, st, n_cu, T); break;
+    case RTW_F_ALL | RTW_F_TREE: wf_run<RTW_F_ALL | RTW_F_TREE>(L, W, st, n_cu, T); break;
     default: wf_run<RTW_F_ALL>(L, W, st, n_cu, T); break;
     }
 }
@@ -2259,6 +2261,7 @@ uint32_t rtw_wavefront_max_waves(int n_cu) {
     mx(wf_grids<RTW_F_TEXTURED>(n_cu).shade, wf_grids<RTW_F_TEXTURED>(n_cu).shade0);
     mx(wf_grids<RTW_F_MEDIA>(n_cu).shade, wf_grids<RTW_F_MEDIA>(n_cu).shade0);
     mx(wf_grids<RTW_F_ALL>(n_cu).shade, wf_grids<RTW_F_ALL>(n_cu).shade0);
+    mx(wf_grids<RTW_F_ALL | RTW_F_TREE>(n_cu).shade, wf_grids<RTW_F_ALL | RTW_F_TREE>(n_cu).shade0);
     return std::max(4 * m, rtw_wf_spheres_max_waves(n_cu));
 }
 #else

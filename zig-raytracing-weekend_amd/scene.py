@@ -217,12 +217,16 @@ class Quad:
 
 @dataclass(eq=False)
 class HittableList:
-    """objects.zig:264-290 (members: Spheres / Quads)."""
+    """objects.zig:264-290 (members: Spheres / Quads).
+
+    bvh: under a transform the library walks a private BVH over the members (``Hittable{.tree}`` in the
+    reference) instead of testing them in turn -- True / False, or None = when there are more than 127."""
     objects: list = field(default_factory=list)
+    bvh: Optional[bool] = None
 
     @staticmethod
-    def init() -> "HittableList":
-        return HittableList([])
+    def init(bvh: Optional[bool] = None) -> "HittableList":
+        return HittableList([], bvh)
 
     def add(self, obj) -> None:
         self.objects.append(obj)
@@ -418,6 +422,8 @@ def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None
             rec["count"] = len(refs)
             rec["n_xf"] = len(xfs)
             rec["flags"] = _abi.RTW_INST_LIST if isinstance(o, HittableList) else 0
+            if isinstance(o, HittableList) and (o.bvh or (o.bvh is None and len(refs) > _abi.RTW_INST_LIST_MAX)):
+                rec["flags"] |= _abi.RTW_INST_BVH
             for j, (k, v) in enumerate(reversed(xfs)):    # xf[0] = innermost
                 rec["xf"][j]["kind"] = k
                 rec["xf"][j]["v"] = v
@@ -505,6 +511,17 @@ class World:
         _abi.check(_abi.lib().rtw_scene_nodes(self.handle, None, 0, C.byref(n)), "rtw_scene_nodes")
         out = np.zeros(n.value, _abi.NODE_DT)
         _abi.check(_abi.lib().rtw_scene_nodes(self.handle, out.ctypes.data, n.value, C.byref(n)), "rtw_scene_nodes")
+        return out
+
+
+    def instance_nodes(self, i: int) -> np.ndarray:
+        """The private BVH of instance i in its object space (rtw_scene_instance_nodes); empty without one."""
+        n = C.c_uint32()
+        f = _abi.lib().rtw_scene_instance_nodes
+        _abi.check(f(self.handle, i, None, 0, C.byref(n)), "rtw_scene_instance_nodes")
+        out = np.zeros(n.value, _abi.NODE_DT)
+        if n.value:
+            _abi.check(f(self.handle, i, out.ctypes.data, n.value, C.byref(n)), "rtw_scene_instance_nodes")
         return out
 
 

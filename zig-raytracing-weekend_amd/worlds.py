@@ -13,8 +13,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from .rng import DOMAIN_SCENE, Stream, f32
-from .scene import (CheckerTexture, ConstantMedium, Dielectric, DiffuseLight, Image, ImageTexture, Lambertian,
-                    Metal, NoiseTexture, Perlin, Quad, RotateY, SolidColor, Sphere, Translate, createBox)
+from .scene import (CheckerTexture, ConstantMedium, Dielectric, DiffuseLight, HittableList, Image, ImageTexture,
+                    Lambertian, Metal, NoiseTexture, Perlin, Quad, RotateY, SolidColor, Sphere, Translate, createBox)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -213,3 +213,49 @@ def cornell_smoke() -> list:
     objs.append(ConstantMedium.initFromColor(box2, 0.01, [1, 1, 1]))
     return objs
 
+
+
+def next_week_world(seed: int = 0, boxes_per_side: int = 20, cluster: int = 1000,
+                    images: Optional[Sequence[Image]] = None) -> list:
+    """The final scene of *Ray Tracing: The Next Week* (not in the reference's main.zig: "Part 2" is an open
+    item of its README), written from the book's description with the reference's objects:
+
+    * boxes_per_side^2 ground boxes of random height (createBox lists at top level);
+    * the quad light, a moving sphere, a glass and a metal sphere;
+    * a glass ball with a blue medium inside it, and the thin white fog around the whole scene;
+    * the earth sphere and a Perlin sphere;
+    * ``cluster`` small white spheres as ONE instance, Translate(RotateY(list, 15), (-100, 270, 395)) --
+      above 127 members the library walks it through a private BVH (RTW_INST_BVH).
+
+    Draws come from the seeded scene stream (a = 6): box heights first, then the cluster's centres."""
+    s = Stream(seed, DOMAIN_SCENE, 6, 0)
+    objs: list = []
+    ground = Lambertian.fromColor([0.48, 0.83, 0.53])
+    w = f32(100.0)
+    for i in range(boxes_per_side):
+        for j in range(boxes_per_side):
+            x0 = f32(f32(-1000.0) + f32(f32(i) * w))
+            z0 = f32(f32(-1000.0) + f32(f32(j) * w))
+            y1 = s.range(1, 101)
+            objs.append(createBox([x0, 0.0, z0], [f32(x0 + w), y1, f32(z0 + w)], ground))
+    light = DiffuseLight.fromColor([7, 7, 7])
+    objs.append(Quad.init([123, 554, 147], [300, 0, 0], [0, 0, 265], light))
+    center1 = np.array([400, 400, 200], np.float32)
+    objs.append(Sphere.initMoving(center1, center1 + np.array([30, 0, 0], np.float32), 50,
+                                  Lambertian.fromColor([0.7, 0.3, 0.1])))
+    objs.append(Sphere.init([260, 150, 45], 50, Dielectric.init(1.5)))
+    objs.append(Sphere.init([0, 150, 145], 50, Metal.fromColor([0.8, 0.8, 0.9], 1.0)))
+    objs.append(Sphere.init([360, 150, 145], 70, Dielectric.init(1.5)))
+    objs.append(ConstantMedium.initFromColor(Sphere.init([360, 150, 145], 70, Dielectric.init(1.5)), 0.2,
+                                             [0.2, 0.4, 0.9]))
+    objs.append(ConstantMedium.initFromColor(Sphere.init([0, 0, 0], 5000, Dielectric.init(1.5)), 0.0001, [1, 1, 1]))
+    if not images:
+        images = [earth_image()]
+    objs.append(Sphere.init([400, 200, 400], 100, Lambertian.init(ImageTexture.init(images, 0))))
+    objs.append(Sphere.init([220, 280, 300], 80, Lambertian.init(NoiseTexture.init(0.2, Perlin.init(seed, 0)))))
+    white = Lambertian.fromColor([0.73, 0.73, 0.73])
+    balls = HittableList.init()
+    for _ in range(cluster):
+        balls.add(Sphere.init(s.vec_range(0, 165), 10, white))
+    objs.append(Translate.init(RotateY.init(balls, 15), [-100, 270, 395]))
+    return objs
