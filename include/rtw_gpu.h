@@ -530,6 +530,30 @@ typedef struct rtw_scene_stats {
     float box_pad;             /* ABI 6: E * 2^-19, the inner-box pad of the FMA slab test (0: exact walk) */
 } rtw_scene_stats;
 int rtw_scene_stats_get(rtw_ctx* ctx, rtw_scene_stats* out);
+
+/* ---------------------------------------------------------------------------
+ * Light importance sampling ("The Rest of Your Life": the mixture density).  With lights
+ * registered, a Lambertian or Isotropic scatter aims half its directions at a uniformly
+ * chosen point of a uniformly chosen light and draws the other half as before, and
+ * weights the path by scattering_pdf / (0.5 light_pdf + 0.5 scattering_pdf): an unbiased
+ * estimator of the same image with less noise where the lights are small.  Emission,
+ * Metal and Dielectric are unchanged; there are no shadow rays.  A caller detects the
+ * capability by the presence of these symbols (the ABI version and every struct are
+ * those of ABI 8).  Only quads can be lights: sphere lights (cone sampling) are out of
+ * scope.
+ * ------------------------------------------------------------------------- */
+#define RTW_MAX_LIGHTS 16
+/* Registers the quads that diffuse scatter samples towards. lights[k] must be a top-level
+ * RTW_OBJ_QUAD of the scene's object list (not an instance member, not a medium boundary) whose
+ * material is RTW_MAT_DIFFUSE_LIGHT; n <= RTW_MAX_LIGHTS. n = 0 (lights may be NULL) clears:
+ * the context then renders exactly as one that never had lights. Must not race a render on
+ * ctx. Works on GPU and host contexts.  Anything else returns RTW_E_INVALID with a message and
+ * leaves the registered lights as they were.  rtw_scene_hash covers the registered list.
+ * rtw_multi_create refuses contexts whose lists differ: each context is given its lights. */
+int rtw_scene_set_lights(rtw_ctx* ctx, const rtw_object* lights, uint32_t n);
+/* Copies the registered lights (out may be NULL to query the count; at most cap are written). */
+int rtw_scene_lights_get(rtw_ctx* ctx, rtw_object* out, uint32_t cap, uint32_t* n_out);
+
 /* Copies the flattened node array (32 B per node) to host. */
 int rtw_scene_nodes(rtw_ctx* ctx, void* out, uint32_t cap, uint32_t* n_out);
 /* Copies the private BVH of instance `instance` (RTW_INST_BVH, or more than 127 members): 32 B per node, the

@@ -34,6 +34,7 @@ RTW_FUSE_STEP, RTW_FUSE_TAIL_LDS, RTW_FUSE_GLOBAL = 1, 2, 4
 RTW_DEAL_RUNS, RTW_DEAL_TAIL, RTW_DEAL_SMALL, RTW_DEAL_ITERS, RTW_DEAL_SINGLES16 = 1, 2, 8, 16, 32
 RTW_DEAL_SMALL_SORT, RTW_DEAL_ALL = 128, 187
 RTW_DEVICE_CPU = -1
+RTW_MAX_LIGHTS = 16
 
 # numpy record layouts == the C structs (asserted against sizeof in tests)
 SPHERE_DT = np.dtype([("center1", "<f4", 3), ("radius", "<f4"), ("center2", "<f4", 3), ("is_moving", "<u4"),
@@ -211,6 +212,8 @@ SIGNATURES = {
     "rtw_scene_flatten": (C.c_int, [C.POINTER(RtwSceneDesc), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
                                     C.POINTER(C.c_uint32)]),
     "rtw_scene_stats_get": (C.c_int, [C.c_void_p, C.POINTER(RtwSceneStats)]),
+    "rtw_scene_set_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rtw_scene_lights_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rtw_scene_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rtw_scene_instance_nodes": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rtw_debug_rng": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),

@@ -26,6 +26,7 @@ int rtw_cpu_render(const rtw_launch& L, uint32_t begin, uint32_t end, float* out
     threads = std::min<uint32_t>(threads, std::max(1u, n));
     std::atomic<bool> stopped{false};
     const bool tree = (L.feat & RTW_F_TREE) != 0;  // instance trees: the instantiation the GPU kernels run
+    const bool pdf = L.n_lights != 0;
     // contiguous chunks, as startRender's Tasks (main.zig:318-324); samples in order per pixel
     auto work = [&](uint32_t t) {
         const uint32_t a = begin + (uint32_t)((uint64_t)n * t / threads);
@@ -44,10 +45,14 @@ int rtw_cpu_render(const rtw_launch& L, uint32_t begin, uint32_t end, float* out
             float* px = out + 4 * (size_t)i;
             float r = px[0], g = px[1], bl = px[2];
             for (uint32_t s = L.s0; s < L.s1; s++) {
-                const f3 c = tree ? sample_radiance<RTW_F_ALL | RTW_F_TREE>(L.nodes, L, pixel, x + L.pixel_offset,
-                                                                            y + L.pixel_offset, s, cnt)
-                                  : sample_radiance<RTW_F_ALL>(L.nodes, L, pixel, x + L.pixel_offset, y + L.pixel_offset, s,
-                                                               cnt);
+                const uint32_t px = x + L.pixel_offset, py = y + L.pixel_offset;
+                f3 c;
+                if (pdf)  // lights registered: the mixture-density instantiations
+                    c = tree ? sample_radiance<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF>(L.nodes, L, pixel, px, py, s, cnt)
+                             : sample_radiance<RTW_F_ALL | RTW_F_PDF>(L.nodes, L, pixel, px, py, s, cnt);
+                else
+                    c = tree ? sample_radiance<RTW_F_ALL | RTW_F_TREE>(L.nodes, L, pixel, px, py, s, cnt)
+                             : sample_radiance<RTW_F_ALL>(L.nodes, L, pixel, px, py, s, cnt);
                 r += c.x;
                 g += c.y;
                 bl += c.z;

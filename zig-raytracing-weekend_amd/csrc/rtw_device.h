@@ -1343,12 +1343,73 @@ RTW_DHD bool needs_unit_vector(uint32_t kind) {
     return false;
 }
 
+// ---------------------------------------------------------------------------
+// Light importance sampling (RTW_F_PDF kernels; rtw_scene_set_lights, DESIGN.md §light sampling).
+// A Lambertian / Isotropic scatter draws its direction from the mixture 0.5 light + 0.5 scatter density
+// and weights the path by pdf_scatter / (0.5 pdf_light + 0.5 pdf_scatter).  Every operation below is
+// plain fp32 in one association, the same on the host and the device (no estimates, no contraction).
+// ---------------------------------------------------------------------------
+// pdf_light of direction d from o: (1/n) sum_k pk, pk = t^2 |d|^2 / (|dot(d, n_k)| / |d| * area_k) where the
+// ray (o, d) meets light k at t >= 0.001 (Quad.hit on its own: occlusion plays no part in a density), else 0
+RTW_DHD float light_pdf(const rtw_launch& L, f3 o, f3 d) {
+    Ray lr;
+    lr.o = o;
+    lr.d = d;
+    lr.time = 0.0f;
+    const float dd = length_squared(d);
+    const float len = __builtin_sqrtf(dd);
+    const uint32_t n = L.n_lights;
+    float sum = 0.0f;
+    for (uint32_t k = 0; k < n; k++) {
+        const rtw_dev_light lt = L.lights[k];
+        const rtw_dev_quad& q = L.quads[lt.quad];
+        float t;
+        if (quad_t(q, lr, kTmin, kInf, t)) {
+            const float cosine = RTW_DIV(__builtin_fabsf(dot(d, ld3(q.n))), len);
+            sum = sum + RTW_DIV((t * t) * dd, cosine * lt.area);
+        }
+    }
+    return RTW_DIV(sum, (float)n);
+}
+
+// The mixture's draws and weight for a diffuse hit whose scatter direction is `dir` and whose scatter density
+// is pdf_scatter(d).  Draw order (after the caller's randomUnitVector, which stays first and unconditional so
+// the wave-shared rejection loops and needs_unit_vector are those of the kernels without lights): s; then,
+// only if s < 0.5, the light k, then a, then b.  False: the sample lies below the horizon (pdf_scatter == 0),
+// the path ends.  Otherwise w = pdf_scatter / (0.5 pdf_light + 0.5 pdf_scatter) <= 2 (the denominator is
+// >= 0.5 pdf_scatter > 0).
+template <bool ISO>
+RTW_DHD bool mixture_scatter(const rtw_launch& L, const HitPrep& h, rtw_rng& rng, f3& dir, float& w) {
+    const uint32_t n = L.n_lights;
+    const float s = rnd(rng);
+    if (s < 0.5f) {
+        uint32_t k = (uint32_t)(rnd(rng) * (float)n);
+        k = k < n - 1u ? k : n - 1u;
+        const float a = rnd(rng);
+        const float b = rnd(rng);
+        const rtw_dev_quad& q = L.quads[L.lights[k].quad];
+        dir = ((ld3(q.q) + splat(a) * ld3(q.u)) + splat(b) * ld3(q.v)) - h.p;
+    }
+    float ps;
+    if constexpr (ISO) {
+        ps = 1.0f / (4.0f * kPi);
+    } else {
+        const float c = dot(h.normal, unit_vector(dir));
+        ps = c > 0.0f ? RTW_DIV(c, kPi) : 0.0f;  // (a NaN cosine -- a zero direction -- ends the path too)
+    }
+    if (!(ps > 0.0f)) return false;
+    const float pl = light_pdf(L, h.p, dir);
+    w = RTW_DIV(ps, 0.5f * pl + 0.5f * ps);
+    return true;
+}
+
 // Material.emitted/scatter (material.zig:18-144) given the hit and, for the
 // materials that draw one, the random unit vector `ruv` (already drawn from rng).
 // Adds thr*emission to acc; returns true with (att, sc) when the ray scatters.
 template <uint32_t FEAT>
 RTW_DHD bool scatter_finish(const rtw_launch& L, const Ray& r, const HitPrep& h, f3 ruv,
                                                rtw_rng& rng, f3 thr, f3& acc, f3& att, Ray& sc) {
+    static_assert((FEAT & RTW_F_PDF) == 0 || (FEAT & RTW_F_ALL) == RTW_F_ALL, "RTW_F_PDF only on top of RTW_F_ALL");
     const rtw_dev_material& m = h.m;
     sc.o = h.p;
     sc.time = r.time;
@@ -1356,6 +1417,15 @@ RTW_DHD bool scatter_finish(const rtw_launch& L, const Ray& r, const HitPrep& h,
     case RTW_MAT_LAMBERTIAN: {  // material.zig:43-54
         f3 dir = h.normal + ruv;
         if (near_zero(dir)) dir = h.normal;
+        if constexpr ((FEAT & RTW_F_PDF) != 0) {
+            if (L.n_lights) {
+                float w;
+                if (!mixture_scatter<false>(L, h, rng, dir, w)) return false;
+                sc.d = dir;
+                att = texture_value<FEAT>(L, m.texture, h.uv, h.p) * splat(w);
+                return true;
+            }
+        }
         sc.d = dir;
         att = texture_value<FEAT>(L, m.texture, h.uv, h.p);
         return true;
@@ -1389,6 +1459,16 @@ RTW_DHD bool scatter_finish(const rtw_launch& L, const Ray& r, const HitPrep& h,
             return false;
         }
         // RTW_MAT_ISOTROPIC (material.zig:139-143)
+        if constexpr ((FEAT & RTW_F_PDF) != 0) {
+            if (L.n_lights) {
+                f3 dir = ruv;
+                float w;
+                if (!mixture_scatter<true>(L, h, rng, dir, w)) return false;
+                sc.d = dir;
+                att = texture_value<FEAT>(L, m.texture, h.uv, h.p) * splat(w);
+                return true;
+            }
+        }
         sc.d = ruv;
         att = texture_value<FEAT>(L, m.texture, h.uv, h.p);
         return true;

@@ -419,6 +419,12 @@ int rtw_scene_create_ex(const rtw_scene_desc* d, int device, const rtw_tuning* t
     L.w2_stack = w2.empty() ? 0u : w2_stack;
     L.inodes = geom.inodes.empty() ? nullptr : reinterpret_cast<const float4*>(dev + o_inod);
     L.hit_bits = hit_bits;
+    L.n_lights = 0;  // rtw_scene_set_lights
+    L.lights = nullptr;
+    ctx->quads_host = geom.quads;  // what rtw_scene_set_lights validates a light against
+    ctx->members_host = geom.members;
+    for (const rtw_dev_medium& m : geom.media) ctx->boundaries_host.push_back(m.boundary);
+    for (uint32_t i = 0; i < d->n_materials; i++) ctx->mat_kind_host.push_back(d->materials[i].kind);
     ctx->inodes_host = geom.inodes;
     ctx->inst_tree.clear();
     for (const rtw_dev_instance& in : geom.insts)
@@ -541,6 +547,7 @@ void rtw_scene_destroy(rtw_ctx* ctx) {
     if (ctx->d_work) (void)hipFree(ctx->d_work);
     if (ctx->d_wf) (void)hipFree(ctx->d_wf);
     if (ctx->d_tl) (void)hipFree(ctx->d_tl);
+    if (ctx->d_lights) (void)hipFree(ctx->d_lights);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -563,7 +570,111 @@ int rtw_scene_flatten(const rtw_scene_desc* d, void* out, uint32_t cap, uint32_t
 
 int rtw_scene_hash(rtw_ctx* ctx, uint64_t* out) {
     if (!ctx || !out) return fail(RTW_E_INVALID, "null ctx");
-    *out = ctx->scene_hash;
+    // the scene image, then the registered lights in order (none: the image's hash as it was): a checkpoint
+    // taken with lights is another estimator's partial sum than one taken without
+    uint64_t h = ctx->scene_hash;
+    if (!ctx->lights.empty()) {
+        const uint32_t n = (uint32_t)ctx->lights.size();
+        auto mix = [&h](uint32_t w) {
+            for (int b = 0; b < 4; b++) h = (h ^ ((w >> (8 * b)) & 0xFFu)) * 0x100000001B3ull;
+        };
+        mix(0x5447494Cu);  // "LIGT"
+        mix(n);
+        for (const rtw_object& o : ctx->lights) {
+            mix(o.kind);
+            mix(o.index);
+        }
+    }
+    *out = h;
+    return RTW_OK;
+}
+
+int rtw_scene_set_lights(rtw_ctx* ctx, const rtw_object* lights, uint32_t n) {
+    if (!ctx) return fail(RTW_E_INVALID, "null ctx");
+    if (n && !lights) return fail(RTW_E_INVALID, "rtw_scene_set_lights: null lights");
+    if (n > RTW_MAX_LIGHTS) return fail(RTW_E_INVALID, "rtw_scene_set_lights: more than RTW_MAX_LIGHTS (16) lights");
+    std::vector<rtw_dev_light> rec(n);
+    char msg[200];
+    for (uint32_t k = 0; k < n; k++) {
+        const rtw_object o = lights[k];
+        if (o.kind != RTW_OBJ_QUAD) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u is not a quad (only quads can be sampled; "
+                          "sphere lights are out of scope)", k);
+            return fail(RTW_E_INVALID, msg);
+        }
+        if (o.index >= ctx->quads_host.size()) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u: quad index %u out of range", k, o.index);
+            return fail(RTW_E_INVALID, msg);
+        }
+        const uint32_t ref = RTW_REF(RTW_OBJ_QUAD, o.index);
+        if (std::find(ctx->members_host.begin(), ctx->members_host.end(), ref) != ctx->members_host.end()) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (quad %u) is an instance member", k, o.index);
+            return fail(RTW_E_INVALID, msg);
+        }
+        if (std::find(ctx->boundaries_host.begin(), ctx->boundaries_host.end(), ref) != ctx->boundaries_host.end()) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (quad %u) is a medium boundary", k, o.index);
+            return fail(RTW_E_INVALID, msg);
+        }
+        bool top = false;  // a leaf of the world tree (the first ordering: object scenes keep one)
+        for (uint32_t i = 0; i < ctx->stats.n_nodes && !top; i++) {
+            uint32_t aw, bz, bw;
+            std::memcpy(&aw, &ctx->nodes_host[i].a[3], 4);
+            std::memcpy(&bz, &ctx->nodes_host[i].b[2], 4);
+            std::memcpy(&bw, &ctx->nodes_host[i].b[3], 4);
+            top = (aw & RTW_LEAF_BIT) && RTW_LEAF_KIND(bw) == RTW_OBJ_QUAD && bz == o.index;
+        }
+        if (!top) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (quad %u) is not in the scene's object list", k,
+                          o.index);
+            return fail(RTW_E_INVALID, msg);
+        }
+        const rtw_dev_quad& q = ctx->quads_host[o.index];
+        if (ctx->mat_kind_host[q.mat] != RTW_MAT_DIFFUSE_LIGHT) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (quad %u): its material is not "
+                          "RTW_MAT_DIFFUSE_LIGHT", k, o.index);
+            return fail(RTW_E_INVALID, msg);
+        }
+        for (uint32_t j = 0; j < k; j++)
+            if (lights[j].index == o.index) {
+                std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: quad %u is listed twice", o.index);
+                return fail(RTW_E_INVALID, msg);
+            }
+        // area = |cross(u, v)| (vec3.zig:31-33 cross, fp32)
+        const float cx = q.u[1] * q.v[2] - q.u[2] * q.v[1], cy = q.u[2] * q.v[0] - q.u[0] * q.v[2],
+                    cz = q.u[0] * q.v[1] - q.u[1] * q.v[0];
+        const float area = std::sqrt(cx * cx + cy * cy + cz * cz);
+        if (!(area > 0.0f) || !std::isfinite(area)) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (quad %u) has no area", k, o.index);
+            return fail(RTW_E_INVALID, msg);
+        }
+        rec[k].quad = o.index;
+        rec[k].area = area;
+    }
+    const bool host = ctx->device == RTW_DEVICE_CPU;
+    if (!host) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        HIP_TRY(hipSetDevice(ctx->device));
+        // a render left on a caller's stream (RTW_RENDER_NO_SYNC) may still read the records
+        if (ctx->last_done) HIP_TRY(hipEventSynchronize(ctx->last_done));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (n && !ctx->d_lights) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->d_lights), RTW_MAX_LIGHTS * sizeof(rtw_dev_light)));
+        if (n) HIP_TRY(hipMemcpy(ctx->d_lights, rec.data(), n * sizeof(rtw_dev_light), hipMemcpyHostToDevice));
+        // the persistent kernel's resident grid is its instantiation's
+        ctx->grid = rtw_persistent_grid(ctx->feat | (n ? RTW_F_PDF : 0u), ctx->stats.n_nodes, (int)ctx->base.waves,
+                                        ctx->base.use_lds != 0);
+    }
+    ctx->lights.assign(lights, lights + n);
+    ctx->lights_rec = rec;
+    ctx->base.n_lights = n;
+    ctx->base.lights = n ? (host ? ctx->lights_rec.data() : ctx->d_lights) : nullptr;
+    return RTW_OK;
+}
+
+int rtw_scene_lights_get(rtw_ctx* ctx, rtw_object* out, uint32_t cap, uint32_t* n_out) {
+    if (!ctx) return fail(RTW_E_INVALID, "null ctx");
+    const uint32_t n = (uint32_t)ctx->lights.size();
+    if (n_out) *n_out = n;
+    if (out && n) std::memcpy(out, ctx->lights.data(), sizeof(rtw_object) * (cap < n ? cap : n));
     return RTW_OK;
 }
 

@@ -88,6 +88,9 @@ struct rtw_launch {
     // per-instance trees (RTW_F_TREE scenes; rtw_bvh.hip InstTreeBuilder), read through L1/L2
     const float4* inodes;        // every instance tree's 32-B nodes, one after the other (rtw_dev_instance.tree)
     uint32_t hit_bits;           // RTW_F_TREE kernels: the hit id is leaf node | member << hit_bits (else 24)
+    // light importance sampling (rtw_scene_set_lights; RTW_F_PDF kernels), read through L1/L2
+    uint32_t n_lights;           // 0: none registered -- the kernels without RTW_F_PDF run
+    const rtw_dev_light* lights; // n_lights records; each light's geometry is quads[lights[k].quad]
 };
 
 #define RTW_TILE_W 16
@@ -106,6 +109,9 @@ struct rtw_launch {
 #define RTW_F_SPHERES 31u   // every sphere-scene feature
 #define RTW_F_ALL 127u
 #define RTW_F_TREE 128u     // some instance has a private BVH (inst_tree_t); only ever set on top of RTW_F_ALL
+#define RTW_F_PDF 256u      // lights are registered (rtw_launch.n_lights > 0): diffuse scatter samples the mixture
+                            // density (scatter_finish); only ever set on top of RTW_F_ALL [| RTW_F_TREE], by the
+                            // dispatchers (rtw_feat_of), never stored in rtw_launch.feat
 
 // max nodes staged in LDS by the persistent kernel (48 KiB)
 #define RTW_MEGA_LDS_NODES_MAX 1536
@@ -114,6 +120,8 @@ struct rtw_kernel_info {
     int blocks_per_cu;
     int n_cu;
 };
+// the features a launch's kernels are picked by: the scene's, | RTW_F_PDF with lights registered
+inline uint32_t rtw_feat_of(const rtw_launch& L) { return L.feat | (L.n_lights ? RTW_F_PDF : 0u); }
 int rtw_persistent_grid(uint32_t feat, uint32_t n_nodes, int waves, bool use_lds);
 
 void rtw_launch_render(const rtw_launch& L, void* stream, int variant, int grid);
@@ -243,6 +251,14 @@ struct rtw_ctx {
     int n_cu = 256;                // compute units of the device (wavefront grids)
     std::vector<hipEvent_t> ev_pool;  // recycled timing events
     uint64_t scene_hash = 0;       // FNV-1a 64 of the uploaded scene image
+    // light importance sampling (rtw_scene_set_lights): the registered list, what validates it (host copies
+    // of the quads, the instance member and medium boundary references, the materials' kinds) and the
+    // device records (GPU context: d_lights, RTW_MAX_LIGHTS records; host context: lights_rec itself)
+    std::vector<rtw_object> lights;
+    std::vector<rtw_dev_light> lights_rec;
+    rtw_dev_light* d_lights = nullptr;
+    std::vector<rtw_dev_quad> quads_host;
+    std::vector<uint32_t> members_host, boundaries_host, mat_kind_host;
     float box_pad = 0;             // absolute pad baked into the inner boxes (SAH trees), 0 = none
     float extent = 0;              // max |coordinate| over the scene's boxes
     // Concurrent callers (the reference's 8 RenderThreads call Camera.render at once, main.zig:314-326):

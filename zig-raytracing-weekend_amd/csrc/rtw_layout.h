@@ -60,6 +60,15 @@ struct rtw_dev_quad {
 };
 static_assert(sizeof(rtw_dev_quad) == 80, "quad record must be 80 bytes");
 
+// 8 B: a registered light (rtw_scene_set_lights).  Its q, u, v, n, d, w are the quad's own record,
+// quads[quad] -- one copy, which rides in the LDS geometry stage wherever the quads do --, beside
+// area = |cross(u, v)| (fp32, computed once on the host)
+struct rtw_dev_light {
+    uint32_t quad;
+    float area;
+};
+static_assert(sizeof(rtw_dev_light) == 8, "light record must be 8 bytes");
+
 // 96 B: members[first .. first+count) (RTW_REF), xf[k] = {bits(kind), a, b, c}:
 // translate (a, b, c) = offset; rotate_y a = sin, b = cos.  xf[0] innermost.
 // tree: 0 = the members are tested one after another (list_t); else 1 + the index in rtw_launch.inodes of the

@@ -242,6 +242,16 @@ int rtw_multi_create(rtw_ctx* const* ctxs, uint32_t n, rtw_multi** out) {
                 delete m;
                 return mfail(RTW_E_INVALID, "two contexts on one device (one context per device)");
             }
+        // every device renders its rows of ONE estimator: the same registered lights, in the same order
+        {
+            const std::vector<rtw_object>&a = ctxs[0]->lights, &b = ctxs[k]->lights;
+            bool same = a.size() == b.size();
+            for (size_t i = 0; same && i < a.size(); i++) same = a[i].kind == b[i].kind && a[i].index == b[i].index;
+            if (!same) {
+                delete m;
+                return mfail(RTW_E_INVALID, "the contexts' light lists differ (rtw_scene_set_lights on each of them)");
+            }
+        }
         m->ctx.push_back(ctxs[k]);
         m->dev.push_back(ctxs[k]->device);
     }

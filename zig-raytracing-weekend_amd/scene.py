@@ -305,6 +305,7 @@ class SceneArrays:
     instances: np.ndarray = field(default_factory=lambda: np.zeros(0, _abi.INSTANCE_DT))
     media: np.ndarray = field(default_factory=lambda: np.zeros(0, _abi.MEDIUM_DT))
     objects: Optional[np.ndarray] = None   # world_objects order; None = every sphere in order
+    lights: Optional[np.ndarray] = None    # rtw_object records World registers (rtw_scene_set_lights); None = none
 
     def desc(self):
         """Build an RtwSceneDesc (keeps the ctypes image array alive on self)."""
@@ -333,9 +334,13 @@ class SceneArrays:
         return d
 
 
-def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None) -> SceneArrays:
+def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None, lights=None) -> SceneArrays:
     """world_objects -> C-ABI records.  bvh_mode: RTW_BVH_SAH (default, fastest) or
     RTW_BVH_REFERENCE (the reference's random-axis median tree, seeded by bvh_seed).
+
+    lights: the quads diffuse scatter samples towards (rtw_scene_set_lights) -- None = none,
+    "emissive" = every top-level Quad whose material is a DiffuseLight, or a list of objects
+    (found by identity among everything flattened; the library validates them).
 
     Every primitive gets its own material record (and textured materials their own
     texture record), in object order; Perlin tables and images are shared by identity.
@@ -381,7 +386,13 @@ def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None
         mats.append(rec)
         return len(mats) - 1
 
+    where = {}   # id(primitive) -> its (kind, index) record, for `lights`
+
     def prim(o) -> tuple:
+        where[id(o)] = ref = new_prim(o)
+        return ref
+
+    def new_prim(o) -> tuple:
         if isinstance(o, Sphere):
             rec = np.zeros((), _abi.SPHERE_DT)
             rec["center1"] = o.center1
@@ -441,6 +452,18 @@ def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None
 
     for o in objects:
         objs.append(hittable(o))
+    light_refs = None
+    if isinstance(lights, str):
+        if lights != "emissive":
+            raise ValueError(f"lights: None, 'emissive' or a list of objects, not {lights!r}")
+        light_refs = [ref for o, ref in zip(objects, objs)
+                      if isinstance(o, Quad) and o.mat.kind == _abi.RTW_MAT_DIFFUSE_LIGHT]
+    elif lights is not None:
+        light_refs = []
+        for o in lights:
+            if id(o) not in where:
+                raise ValueError("lights: an object that is not in the scene")
+            light_refs.append(where[id(o)])
     pl = np.zeros(len(perlins), _abi.PERLIN_DT)
     for i, p in enumerate(perlins):
         pl[i]["ranvec"] = p.ranvec
@@ -455,7 +478,8 @@ def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None
                        images, bvh_seed, _abi.RTW_BVH_SAH if bvh_mode is None else bvh_mode,
                        quads=arr(quads, _abi.QUAD_DT), members=arr(members, _abi.OBJECT_DT),
                        instances=arr(instances, _abi.INSTANCE_DT), media=arr(media, _abi.MEDIUM_DT),
-                       objects=None if only_spheres else arr(objs, _abi.OBJECT_DT))
+                       objects=None if only_spheres else arr(objs, _abi.OBJECT_DT),
+                       lights=None if light_refs is None else arr(light_refs, _abi.OBJECT_DT))
 
 
 def flatten_bvh(arrays: SceneArrays) -> np.ndarray:
@@ -489,6 +513,31 @@ class World:
         else:
             _abi.check(L.rtw_scene_create(C.byref(self._desc), device, C.byref(h)), "rtw_scene_create")
         self.handle = h
+        if arrays.lights is not None and len(arrays.lights):
+            try:
+                self.set_lights(arrays.lights)
+            except Exception:
+                self.close()
+                raise
+
+    def set_lights(self, lights) -> None:
+        """rtw_scene_set_lights: the quads diffuse scatter samples towards -- an OBJECT_DT array, (kind, index)
+        pairs, or None / empty to clear (the world then renders exactly as one never given lights).  Must not
+        race a render on this world."""
+        recs = np.zeros(0, _abi.OBJECT_DT) if lights is None else np.ascontiguousarray(
+            lights if isinstance(lights, np.ndarray) and lights.dtype == _abi.OBJECT_DT
+            else np.array([tuple(int(x) for x in o) for o in lights], _abi.OBJECT_DT).reshape(-1))
+        _abi.check(_abi.lib().rtw_scene_set_lights(self.handle, _abi.ptr(recs), len(recs)), "rtw_scene_set_lights")
+
+    def lights(self) -> np.ndarray:
+        """The registered lights (rtw_scene_lights_get) as OBJECT_DT records."""
+        n = C.c_uint32()
+        f = _abi.lib().rtw_scene_lights_get
+        _abi.check(f(self.handle, None, 0, C.byref(n)), "rtw_scene_lights_get")
+        out = np.zeros(n.value, _abi.OBJECT_DT)
+        if n.value:
+            _abi.check(f(self.handle, out.ctypes.data, n.value, C.byref(n)), "rtw_scene_lights_get")
+        return out
 
     def close(self):
         if getattr(self, "handle", None) and self.handle.value:
