@@ -574,6 +574,18 @@ int rtw_debug_sample(rtw_ctx* ctx, const rtw_camera* cam, uint64_t seed, uint32_
  * checks that the filter never rejects a test the exact arithmetic accepts. */
 int rtw_debug_sphere_filter(uint32_t n, const float* a, const float* half_b, const float* c, const float* closest,
                             uint8_t* may_hit, uint8_t* accept);
+/* Host-only (detected by the symbol's presence; the ABI version and every struct are those of ABI 8): the slot
+ * arithmetic of the coherent queues' per-wave cursors, the device's code, for n pushing lanes.  A bucket's open
+ * block is [blk, blk + 64) and old[i] what the lane's atomic add of 1 on the bucket's cursor returned; fresh[i] is
+ * the first slot of the block the bucket opens if it overflows.  over[i] = 0xFFFFFFFF and slot[i] = old[i] inside
+ * the block; past it over[i] = j = old[i] - (blk[i] + 64), the lane's index in the fresh block, and slot[i] =
+ * fresh[i] + j.  rebase[i] is what the lane with j = 0 adds to the cursor so that it continues in the fresh block. */
+int rtw_debug_push_cursor(uint32_t n, const uint32_t* blk, const uint32_t* old, const uint32_t* fresh,
+                          uint32_t* slot, uint32_t* over, uint32_t* rebase);
+/* GPU contexts, after a wavefront render: the stripe capacity (slots) of its last batch and the 3 x 256 stripe
+ * counters (slots used per output stripe, of the last iterations' queues; a set already reset reads 0).  No
+ * counter may exceed the capacity: the queues are not bound-checked on the device. */
+int rtw_debug_stripe_counters(rtw_ctx* ctx, uint32_t* stripe_cap, uint32_t counters[768]);
 
 #ifdef __cplusplus
 }

@@ -219,6 +219,9 @@ SIGNATURES = {
     "rtw_debug_rng": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "rtw_debug_sample": (C.c_int, [C.c_void_p, C.POINTER(RtwCamera), C.c_uint64, C.c_uint32, C.c_uint32,
                                    C.c_void_p]),
+    "rtw_debug_push_cursor": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "rtw_debug_stripe_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
 }
 
 _lib = None

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "rtw_device.h"
+#include "rtw_wavefront.h"
 
 int rtw_cpu_render(const rtw_launch& L, uint32_t begin, uint32_t end, float* out, uint32_t threads,
                    const rtw_render_opts* stop) {
@@ -95,6 +96,19 @@ extern "C" int rtw_debug_sphere_filter(uint32_t n, const float* a, const float* 
             }
         }
         accept[i] = ok ? 1 : 0;
+    }
+    return RTW_OK;
+}
+
+// Host-only test hook (include/rtw_gpu.h): the slot arithmetic of the bucketed push's LDS cursors
+// (rtw_wavefront.h wf_cursor_*, the device's code) for n pushing lanes
+extern "C" int rtw_debug_push_cursor(uint32_t n, const uint32_t* blk, const uint32_t* old, const uint32_t* fresh,
+                                     uint32_t* slot, uint32_t* over, uint32_t* rebase) {
+    if (n && (!blk || !old || !fresh || !slot || !over || !rebase)) return RTW_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        over[i] = wf_cursor_over(blk[i], old[i]);
+        slot[i] = wf_cursor_slot(blk[i], old[i], fresh[i]);
+        rebase[i] = wf_cursor_rebase(blk[i], fresh[i]);
     }
     return RTW_OK;
 }

@@ -237,7 +237,7 @@ int rtw_scene_create_ex(const rtw_scene_desc* d, int device, const rtw_tuning* t
     const uint32_t sfeat = scene_features(d);
     const size_t mat_b = (size_t)d->n_materials * sizeof(rtw_dev_material);
     if (orders == 8 && !tu.bvh_orders && tu.compact_nodes == 1 && tu.fast_box && !(sfeat & ~RTW_F_CHECKER) &&
-        (2 * (size_t)d->n_spheres + 8) * 4 * 16 + mat_b <= RTW_WF_CLDS2_MAX)
+        (2 * (size_t)d->n_spheres + 8) * 4 * 16 + mat_b + RTW_WF_CURSOR_BYTES(768u) <= RTW_WF_CLDS2_MAX)
         orders = 4;
     // (object scenes keep one ordering: their hit ids carry an instance member where sphere scenes carry the copy)
     if (tu.bvh_orders) orders = (d->bvh_mode == RTW_BVH_SAH && !objects && tu.bvh_orders > 1) ? tu.bvh_orders : 1u;
@@ -862,6 +862,8 @@ int run_wavefront(rtw_ctx* ctx, rtw_launch L, hipStream_t stream, rtw_timer* T) 
         W.n_s = L.s1 - L.s0;
         W.n_paths = (uint32_t)(n_pix * W.n_s);
         W.stripe_cap = (uint32_t)stripe_cap(W.n_paths);
+        ctx->wf_len = W.len[0];
+        ctx->wf_stripe_cap = W.stripe_cap;
         rtw_wavefront_batch(L, W, stream, ctx->n_cu, T);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "wavefront launch");
@@ -1298,6 +1300,21 @@ int rtw_debug_sample(rtw_ctx* ctx, const rtw_camera* cam, uint64_t seed, uint32_
     out[0] = tmp[0];
     out[1] = tmp[1];
     out[2] = tmp[2];
+    return RTW_OK;
+}
+
+int rtw_debug_stripe_counters(rtw_ctx* ctx, uint32_t* stripe_cap, uint32_t* counters) {
+    if (!ctx || !stripe_cap || !counters) return fail(RTW_E_INVALID, "null args");
+    if (ctx->device == RTW_DEVICE_CPU) return fail(RTW_E_INVALID, "host context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (!ctx->wf_len || !ctx->d_wf) return fail(RTW_E_INVALID, "no wavefront render yet");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipDeviceSynchronize());
+    // (the three sets are consecutive 256-B-aligned takes of run_wavefront's layout)
+    std::vector<uint32_t> raw(3u * RTW_WF_STRIPES * RTW_WF_LEN_STRIDE);
+    HIP_TRY(hipMemcpy(raw.data(), ctx->wf_len, raw.size() * 4, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < 3u * RTW_WF_STRIPES; k++) counters[k] = raw[(size_t)k * RTW_WF_LEN_STRIDE];
+    *stripe_cap = ctx->wf_stripe_cap;
     return RTW_OK;
 }
 

@@ -241,6 +241,8 @@ struct rtw_ctx {
     uint64_t tl_cap = 0;
     void* d_wf = nullptr;          // wavefront path state (rtw_wavefront.h), wf_cap paths
     uint64_t wf_cap = 0;
+    uint32_t* wf_len = nullptr;    // the last batch's stripe counters (3 sets) and capacity: rtw_debug_stripe_counters
+    uint32_t wf_stripe_cap = 0;
     uint64_t wf_max_paths = 1u << 26;  // paths per wavefront batch (x RTW_WF_PATH_BYTES); set at scene creation
     uint32_t wf_iters = 9;         // wavefront bounces before the tail kernel (rtw_tuning.wf_iters)
     uint32_t wf_sort_mask = 15;    // their bucket key bits (rtw_tuning.sort_bits)

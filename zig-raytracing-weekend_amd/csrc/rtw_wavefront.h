@@ -11,6 +11,23 @@
 // coherent queues (wf_push_bucketed): a wave keeps one open 64-slot block per direction bucket
 #define RTW_WF_BUCKET_BITS 4
 #define RTW_WF_BUCKETS (1u << RTW_WF_BUCKET_BITS)
+// static LDS of a pushing kernel of `threads` threads: per wave and bucket the open block and its cursor
+#define RTW_WF_CURSOR_BYTES(threads) ((threads) / 64u * 2u * RTW_WF_BUCKETS * 4u)
+
+// The slot arithmetic of those cursors (host and device: rtw_debug_push_cursor runs it on the host).  A bucket's
+// open block is [blk, blk + 64) and `old` the value a pushing lane's atomic add of 1 on the bucket's cursor
+// returned.  Inside the block it is the lane's slot.  Past it the lane is number j = old - (blk + 64) of those
+// that overflow into the bucket's fresh block: lane j = 0 opens that block at `fresh` and moves the cursor there
+// (wf_cursor_rebase), every lane j takes slot fresh + j (j < 64: a push has 64 lanes, so one fresh block holds them).
+#define RTW_WF_NO_OVER 0xFFFFFFFFu
+__host__ __device__ inline uint32_t wf_cursor_over(uint32_t blk, uint32_t old) {
+    return old < blk + 64u ? RTW_WF_NO_OVER : old - (blk + 64u);
+}
+__host__ __device__ inline uint32_t wf_cursor_slot(uint32_t blk, uint32_t old, uint32_t fresh) {
+    return old < blk + 64u ? old : fresh + (old - (blk + 64u));
+}
+// what lane j = 0 adds to the cursor: it then counts on in the fresh block
+__host__ __device__ inline uint32_t wf_cursor_rebase(uint32_t blk, uint32_t fresh) { return fresh - (blk + 64u); }
 #define RTW_TL_MAX 128         // camera-ray candidate list capacity per 8x8 tile (rtw_tuning.tile_lists caps it)
 #define RTW_TL_WALK 0xFFFFFFFFu
 #define RTW_TL_BYTES (RTW_TL_MAX * 32 + 4)  // per tile

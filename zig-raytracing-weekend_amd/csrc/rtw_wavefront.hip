@@ -276,10 +276,12 @@ __device__ __forceinline__ uint32_t wf_push(const rtw_wf& W, uint32_t it, bool p
 // direction's x and z and four levels of its elevation), so a block -- one chunk of the next iteration --
 // holds rays of similar direction that left the few tiles the wave worked on: the walks of a wave then
 // take similar paths through the tree (tools/diag_sort.py: C2 iteration 1 walk lane utilisation 0.60 as
-// appended, 0.78 tile + direction).  The open blocks live in the lanes: lane b holds
-// bucket b's block (first slot `bb`, slots used `bf`; 64 = none).  Per push: lanes with equal keys by
-// one ballot per key bit; each bucket's lanes take consecutive slots of its block, and buckets whose
-// block overflows take fresh blocks, all of them with one atomic on the stripe counter.  A partly filled
+// appended, 0.78 tile + direction).  The open blocks are per-wave cursors in LDS, which the
+// VALU-bound step leaves idle: per bucket the block's first slot `blk` and the next free slot `cur`
+// (cur == blk + 64: no open block).  Per push: each lane adds 1 to its bucket's cursor (an LDS atomic: lanes
+// of one bucket get consecutive slots); values past the block's end index a fresh block, which the lane that
+// got exactly the end opens -- all the wave's fresh blocks with one atomic on the stripe counter -- and the
+// bucket's other overflow lanes read back (rtw_wavefront.h wf_cursor_*).  A partly filled
 // block's unused slots are marked dead (depth 0) when the wave's iteration ends (wf_close_blocks).
 // vec3.randomInUnitSphere (vec3.zig:40-45) for every lane of the wave with `need`, cooperatively: the
 // same accepted candidate and the same final RNG state as seq_reject<3> per lane.  The draws are
@@ -370,50 +372,58 @@ __device__ __forceinline__ uint32_t wf_bucket(f3 d) {
     return (d.x < 0.0f ? 1u : 0u) | (d.z < 0.0f ? 2u : 0u) | (qy << 2);
 }
 
+// this wave's cursors (`cs`, LDS): cs[b] = bucket b's next free slot, cs[RTW_WF_BUCKETS + b] = its open block
+__device__ __forceinline__ uint32_t wf_cs_load(const uint32_t* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+__device__ __forceinline__ void wf_cs_store(uint32_t* p, uint32_t v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+// (the wave's lanes run in lockstep: the fence orders its LDS accesses for the compiler and the LDS queue)
+__device__ __forceinline__ void wf_cs_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
+
+// this wave's cursors in a kernel of T threads: static LDS (RTW_WF_CURSOR_BYTES(T): 512 B at 256 threads, 1.5 KB
+// at 768, 2 KB at 1024), which the occupancy queries (wf_grid) and the stages' fit rules count
+template <uint32_t T>
+__device__ __forceinline__ uint32_t* wf_cursors() {
+    __shared__ uint32_t cursors[RTW_WF_CURSOR_BYTES(T) / 4u];
+    return cursors + (threadIdx.x >> 6) * (2u * RTW_WF_BUCKETS);
+}
+
+// no bucket has an open block (before the wave's chunk loop)
+__device__ __forceinline__ void wf_open_cursors(uint32_t* cs) {
+    if (__lane_id() < RTW_WF_BUCKETS) {
+        wf_cs_store(cs + __lane_id(), 64u);
+        wf_cs_store(cs + RTW_WF_BUCKETS + __lane_id(), 0u);
+    }
+    wf_cs_fence();
+}
+
 __device__ __forceinline__ uint32_t wf_push_bucketed(const rtw_wf& W, uint32_t it, bool push, uint32_t key,
-                                                     uint32_t& bb, uint32_t& bf) {
-    const uint64_t act = __ballot(push);
-    if (!act) return 0;
-    const uint32_t lane = __lane_id();
-    key = push ? key : 0u;
-    uint64_t eq = act, eqh = act;  // eq: lanes with my key; eqh: lanes whose key is my lane (holder view)
-#pragma unroll
-    for (uint32_t k = 0; k < RTW_WF_BUCKET_BITS; k++) {
-        const uint64_t m = __ballot(push && ((key >> k) & 1u));
-        eq &= ((key >> k) & 1u) ? m : ~m;
-        eqh &= ((lane >> k) & 1u) ? m : ~m;
+                                                     uint32_t* cs) {
+    uint32_t old = 0, blk = 0, j = RTW_WF_NO_OVER;
+    if (push) {
+        old = __hip_atomic_fetch_add(cs + key, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        blk = wf_cs_load(cs + RTW_WF_BUCKETS + key);
+        j = wf_cursor_over(blk, old);
     }
-    if (lane >= RTW_WF_BUCKETS) eqh = 0;
-    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    const uint32_t rank = (uint32_t)__popcll(eq & lt), cnt = (uint32_t)__popcll(eq);
-    const uint32_t leader = (uint32_t)__builtin_ctzll(eq | (1ull << 63));  // push lanes: eq != 0
-    const uint32_t base = __shfl(bb, (int)key), fill = __shfl(bf, (int)key);  // my bucket's open block
-    const uint32_t room = 64u - fill;
-    // buckets whose block cannot take all their lanes get a fresh block (one atomic for the wave)
-    const uint64_t need = __ballot(push && rank == 0 && cnt > room);
+    // buckets whose block is full get a fresh block each (one atomic for the wave): the lane with j == 0 opens it
+    const uint64_t need = __ballot(j == 0u);
+    if (!need) return old;  // (an overflowing bucket has its j == 0 lane in this push)
+    const uint32_t s = wf_wave() % RTW_WF_STRIPES, lane = __lane_id();
+    uint32_t* len = &W.len[(it + 1u) % 3u][s * RTW_WF_LEN_STRIDE];
     uint32_t b0 = 0;
-    if (need) {
-        const uint32_t s = wf_wave() % RTW_WF_STRIPES;
-        uint32_t* len = &W.len[(it + 1u) % 3u][s * RTW_WF_LEN_STRIDE];
-        if (lane == 0) b0 = atomicAdd(len, 64u * (uint32_t)__popcll(need));
-        b0 = s * W.stripe_cap + __shfl(b0, 0);
+    if (lane == 0) b0 = atomicAdd(len, 64u * (uint32_t)__popcll(need));
+    b0 = s * W.stripe_cap + __shfl(b0, 0);
+    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    uint32_t fresh = b0 + 64u * (uint32_t)__popcll(need & lt);
+    if (j == 0u) {
+        wf_cs_store(cs + RTW_WF_BUCKETS + key, fresh);
+        __hip_atomic_fetch_add(cs + key, wf_cursor_rebase(blk, fresh), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     }
-    const uint64_t llt = leader >= 63 ? (need & ~(1ull << 63)) : (need & ((1ull << leader) - 1ull));
-    const uint32_t fresh = b0 + 64u * (uint32_t)__popcll(llt);  // my bucket's fresh block, if it took one
-    // holder lanes: the new state of their bucket
-    const uint32_t hc = (uint32_t)__popcll(eqh);
-    if (hc) {
-        const uint32_t hl = (uint32_t)__builtin_ctzll(eqh);
-        const uint64_t hlt = hl == 0 ? 0ull : (need & (~0ull >> (64 - hl)));
-        const uint32_t hroom = 64u - bf;
-        if (hc <= hroom) {
-            bf += hc;
-        } else {
-            bb = b0 + 64u * (uint32_t)__popcll(hlt);
-            bf = hc - hroom;
-        }
-    }
-    return rank < room ? base + fill + rank : fresh + (rank - room);
+    wf_cs_fence();
+    if (j != RTW_WF_NO_OVER && j != 0u) fresh = wf_cs_load(cs + RTW_WF_BUCKETS + key);
+    return wf_cursor_slot(blk, old, fresh);
 }
 
 // packed path state (see wf_load_ray_it)
@@ -434,14 +444,20 @@ __device__ __forceinline__ uint32_t wf_iter_depth(const rtw_launch& L, uint32_t 
 // the unused slots of the wave's partly filled blocks: dead (depth 0; packed state: d = 0), so the next
 // iteration skips them
 template <uint32_t FEAT>
-__device__ __forceinline__ void wf_close_blocks(const rtw_wf& W, uint32_t it, uint32_t bb, uint32_t bf, bool pk) {
+__device__ __forceinline__ void wf_close_blocks(const rtw_wf& W, uint32_t it, const uint32_t* cs, bool pk) {
     const rtw_wf_set& O = W.set[(it + 1u) & 1u];
-    uint64_t open = __ballot(__lane_id() < RTW_WF_BUCKETS && bf > 0u && bf < 64u);
+    wf_cs_fence();
+    uint32_t bb = 0, bc = 64u;  // lane b: bucket b's open block and cursor; its dead slots are [bc, bb + 64)
+    if (__lane_id() < RTW_WF_BUCKETS) {
+        bc = wf_cs_load(cs + __lane_id());
+        bb = wf_cs_load(cs + RTW_WF_BUCKETS + __lane_id());
+    }
+    uint64_t open = __ballot(bc < bb + 64u);
     while (open) {
         const uint32_t h = (uint32_t)__builtin_ctzll(open);
         open &= open - 1ull;
-        const uint32_t base = __shfl(bb, (int)h), fill = __shfl(bf, (int)h);
-        if (__lane_id() >= fill) {
+        const uint32_t base = __shfl(bb, (int)h), cur = __shfl(bc, (int)h);
+        if (base + __lane_id() >= cur) {
             O.ray_d[base + __lane_id()] = make_float4(0, 0, 0, 0);
             if (wf_packed<FEAT>() && pk) O.ray_o[base + __lane_id()] = make_float4(0, 0, 0, 0);
         }
@@ -1101,28 +1117,29 @@ __global__ __launch_bounds__(1024) void wf_trace_clds(rtw_launch L, rtw_wf W, ui
 // shade: emission / background and Material.scatter; a surviving path's state
 // moves to its slot in the other set; an ending path stores its radiance by id
 template <uint32_t FEAT, bool CAM>
-__device__ __forceinline__ void wf_shade_body(const rtw_launch& L, const rtw_wf& W, uint32_t it);
+__device__ __forceinline__ void wf_shade_body(const rtw_launch& L, const rtw_wf& W, uint32_t it, uint32_t* cs);
 
 template <uint32_t FEAT, bool CAM = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wf_split_wpe<FEAT>(RTW_WPE_SHADE)))) void wf_shade(rtw_launch L, rtw_wf W, uint32_t it) {
+    uint32_t* cs = wf_cursors<256>();
     if constexpr ((FEAT & RTW_F_GEOM) != 0) {
         if (L.geom_lds) {  // quads / members / instances in LDS (hit records of object scenes)
             extern __shared__ float4 wf_shade_geom[];
             const rtw_launch G = stage_geom(L, wf_shade_geom);
             __syncthreads();
-            wf_shade_body<FEAT, CAM>(G, W, it);
+            wf_shade_body<FEAT, CAM>(G, W, it, cs);
             return;
         }
     }
-    wf_shade_body<FEAT, CAM>(L, W, it);
+    wf_shade_body<FEAT, CAM>(L, W, it, cs);
 }
 
 template <uint32_t FEAT, bool CAM>
-__device__ __forceinline__ void wf_shade_body(const rtw_launch& L, const rtw_wf& W, uint32_t it) {
+__device__ __forceinline__ void wf_shade_body(const rtw_launch& L, const rtw_wf& W, uint32_t it, uint32_t* cs) {
     const rtw_wf_set& S = W.set[it & 1u];
     const rtw_wf_set& O = W.set[(it + 1u) & 1u];
     const bool bucketed = it < W.sort_iters;
-    uint32_t bb = 0, bf = 64;  // lane b: bucket b's open block (wf_push_bucketed)
+    if (bucketed) wf_open_cursors(cs);
     for (WfIter e(W, it); e.more(); e.next()) {
         bool push = false;
         uint32_t slot = 0, pid = 0, depth = 0;
@@ -1181,11 +1198,11 @@ __device__ __forceinline__ void wf_shade_body(const rtw_launch& L, const rtw_wf&
         }
         if (depth && !push) W.ls[pid] = rtw_rgb{acc.x, acc.y, acc.z};
         if (CAM && !depth) W.ls[slot] = rtw_rgb{0.0f, 0.0f, 0.0f};  // padding, rayColor(r, 0) = 0
-        const uint32_t out = bucketed ? wf_push_bucketed(W, it, push, push ? wf_bucket(sc.d) & W.sort_mask : 0u, bb, bf)
+        const uint32_t out = bucketed ? wf_push_bucketed(W, it, push, push ? wf_bucket(sc.d) & W.sort_mask : 0u, cs)
                                       : wf_push(W, it, push);
         if (push) wf_store_path<FEAT>(O, out, sc, depth - 1, thr, rng.s, pid, acc, true);
     }
-    if (bucketed) wf_close_blocks<FEAT>(W, it, bb, bf, true);
+    if (bucketed) wf_close_blocks<FEAT>(W, it, cs, true);
 }
 
 // tail: the paths still queued after the last wavefront iteration, each to
@@ -1500,14 +1517,15 @@ constexpr bool wf_late_rest() {
 
 // IT0: 1 = the launch of iteration 0 (camera rays), 0 = a launch of iteration >= 1, 2 = either (runtime `it`)
 template <uint32_t FEAT, int WALK, int CNT = 2, int IT0 = 2>
-__device__ __forceinline__ void wf_step_body(const rtw_launch& L, const rtw_wf& W, uint32_t it, const void* lds) {
+__device__ __forceinline__ void wf_step_body(const rtw_launch& L, const rtw_wf& W, uint32_t it, const void* lds,
+                                             uint32_t* cs) {
     if constexpr (IT0 == 1) it = 0;  // (the compiler then drops the other iterations' code)
     const bool first = IT0 == 2 ? it == 0 : IT0 == 1;
     const rtw_wf_set& S = W.set[it & 1u];
     const rtw_wf_set& O = W.set[(it + 1u) & 1u];
     Counters cnt;
     const bool bucketed = it < W.sort_iters;
-    uint32_t bb = 0, bf = 64;  // lane b: bucket b's open block (wf_push_bucketed)
+    if (bucketed) wf_open_cursors(cs);
     for (WfIter e(W, it); e.more(); e.next()) {  // wave-uniform: the body starts converged
         bool live = false, push = false;
         uint32_t slot = 0, pid = 0, depth = 0;
@@ -1650,11 +1668,11 @@ __device__ __forceinline__ void wf_step_body(const rtw_launch& L, const rtw_wf& 
             }
         }
         if (live && !push) W.ls[pid] = rtw_rgb{acc.x, acc.y, acc.z};
-        const uint32_t out = bucketed ? wf_push_bucketed(W, it, push, push ? wf_bucket(sc.d) & W.sort_mask : 0u, bb, bf)
+        const uint32_t out = bucketed ? wf_push_bucketed(W, it, push, push ? wf_bucket(sc.d) & W.sort_mask : 0u, cs)
                                       : wf_push(W, it, push);
         if (push) wf_store_path<FEAT>(O, out, sc, depth - 1, thr, rng.s, pid, acc, true);
     }
-    if (bucketed) wf_close_blocks<FEAT>(W, it, bb, bf, true);
+    if (bucketed) wf_close_blocks<FEAT>(W, it, cs, true);
     if constexpr (CNT != 0) flush_counters(L, cnt, 0);
 }
 
@@ -1664,7 +1682,7 @@ __device__ __forceinline__ void wf_step_zero_next(const rtw_wf& W, uint32_t it) 
 
 // compact nodes of every copy in LDS, then the materials when they fit
 template <uint32_t FEAT, int WALK, int CNT = 2, int IT0 = 2>
-__device__ __forceinline__ void wf_step_clds_body(const rtw_launch& L, const rtw_wf& W, uint32_t it) {
+__device__ __forceinline__ void wf_step_clds_body(const rtw_launch& L, const rtw_wf& W, uint32_t it, uint32_t* cs) {
     wf_step_zero_next(W, it);
     extern __shared__ uint4 wf_clds[];
     stage_clds(L, wf_clds);
@@ -1675,17 +1693,17 @@ __device__ __forceinline__ void wf_step_clds_body(const rtw_launch& L, const rtw
         __syncthreads();
         rtw_launch Lm = L;
         Lm.mats = reinterpret_cast<const rtw_dev_material*>(ml);
-        wf_step_body<FEAT, WALK, CNT, IT0>(Lm, W, it, wf_clds);
+        wf_step_body<FEAT, WALK, CNT, IT0>(Lm, W, it, wf_clds, cs);
         return;
     }
-    wf_step_body<FEAT, WALK, CNT, IT0>(L, W, it, wf_clds);
+    wf_step_body<FEAT, WALK, CNT, IT0>(L, W, it, wf_clds, cs);
 }
 
 // one 1024-thread block per CU (the 8-copy stage, 124 KB for C2, allows no second block)
 template <uint32_t FEAT, int CN = CN_F16_8>
 __global__ __launch_bounds__(1024) void wf_step_clds(rtw_launch L, rtw_wf W, uint32_t it) {
     static_assert((FEAT & (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_MOVING)) == 0, "static sphere scenes");
-    wf_step_clds_body<FEAT, CN == CN_F32_4 ? WALK_CLDS32 : CN == CN_F16_4 ? WALK_CLDS4 : WALK_CLDS>(L, W, it);
+    wf_step_clds_body<FEAT, CN == CN_F32_4 ? WALK_CLDS32 : CN == CN_F16_4 ? WALK_CLDS4 : WALK_CLDS>(L, W, it, wf_cursors<1024>());
 }
 
 // The 4-copy stage (C2: 62 KB + 15.5 KB of materials) at two blocks of T = 768 threads per CU (rtw_tuning.clds_shape
@@ -1703,13 +1721,14 @@ template <uint32_t FEAT, uint32_t T, int CNT = 2, int IT0 = 2>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(2 * T / 256)))
 void wf_step_clds2(rtw_launch L, rtw_wf W, uint32_t it) {
     static_assert((FEAT & (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_MOVING)) == 0, "static sphere scenes");
-    wf_step_clds_body<FEAT, WALK_CLDS4, CNT, IT0>(L, W, it);
+    wf_step_clds_body<FEAT, WALK_CLDS4, CNT, IT0>(L, W, it, wf_cursors<T>());
 }
 
 // wf_step's LDS extras by mask (bit 0 Perlin tables, 1 materials/textures, 2 geometry); masks a
 // scene class cannot use compile to nothing
 template <uint32_t FEAT, uint32_t MASK, int CNT, int IT0>
 __device__ __forceinline__ void wf_step_staged(const rtw_launch& L, const rtw_wf& W, uint32_t it, float4* nodes,
+                                               uint32_t* cs,
                                                float4* extra) {
     constexpr bool P = (MASK & 1u) && (FEAT & RTW_F_NOISE), S = (MASK & 2u) != 0, G = (MASK & 4u) && (FEAT & RTW_F_GEOM);
     if constexpr (P || S || G) {
@@ -1726,7 +1745,7 @@ __device__ __forceinline__ void wf_step_staged(const rtw_launch& L, const rtw_wf
         }
         if constexpr (G) Lp = stage_geom(Lp, extra);
         __syncthreads();
-        wf_step_body<FEAT, WALK_LDS, CNT, IT0>(Lp, W, it, nodes);
+        wf_step_body<FEAT, WALK_LDS, CNT, IT0>(Lp, W, it, nodes, cs);
     }
 }
 
@@ -1734,6 +1753,7 @@ __device__ __forceinline__ void wf_step_staged(const rtw_launch& L, const rtw_wf
 template <uint32_t FEAT, bool LDS, int CNT = 2, int IT0 = 2>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RTW_WPE_STEP))) void wf_step(rtw_launch L, rtw_wf W, uint32_t it) {
     wf_step_zero_next(W, it);
+    uint32_t* cs = wf_cursors<256>();
     extern __shared__ float4 wf_lds_nodes[];
     const uint32_t n4 = LDS ? 2u * L.n_nodes * L.n_orders : 0u;
     if constexpr (LDS) {
@@ -1744,19 +1764,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RTW_WPE_STE
                               (((FEAT & RTW_F_GEOM) && L.geom_lds) ? 4u : 0u);
         float4* extra = wf_lds_nodes + n4;
         switch (mask) {
-            case 1: return wf_step_staged<FEAT, 1, CNT, IT0>(L, W, it, wf_lds_nodes, extra);
-            case 2: return wf_step_staged<FEAT, 2, CNT, IT0>(L, W, it, wf_lds_nodes, extra);
-            case 3: return wf_step_staged<FEAT, 3, CNT, IT0>(L, W, it, wf_lds_nodes, extra);
-            case 4: return wf_step_staged<FEAT, 4, CNT, IT0>(L, W, it, wf_lds_nodes, extra);
-            case 5: return wf_step_staged<FEAT, 5, CNT, IT0>(L, W, it, wf_lds_nodes, extra);
-            case 6: return wf_step_staged<FEAT, 6, CNT, IT0>(L, W, it, wf_lds_nodes, extra);
-            case 7: return wf_step_staged<FEAT, 7, CNT, IT0>(L, W, it, wf_lds_nodes, extra);
+            case 1: return wf_step_staged<FEAT, 1, CNT, IT0>(L, W, it, wf_lds_nodes, cs, extra);
+            case 2: return wf_step_staged<FEAT, 2, CNT, IT0>(L, W, it, wf_lds_nodes, cs, extra);
+            case 3: return wf_step_staged<FEAT, 3, CNT, IT0>(L, W, it, wf_lds_nodes, cs, extra);
+            case 4: return wf_step_staged<FEAT, 4, CNT, IT0>(L, W, it, wf_lds_nodes, cs, extra);
+            case 5: return wf_step_staged<FEAT, 5, CNT, IT0>(L, W, it, wf_lds_nodes, cs, extra);
+            case 6: return wf_step_staged<FEAT, 6, CNT, IT0>(L, W, it, wf_lds_nodes, cs, extra);
+            case 7: return wf_step_staged<FEAT, 7, CNT, IT0>(L, W, it, wf_lds_nodes, cs, extra);
             default: break;
         }
         __syncthreads();
-        wf_step_body<FEAT, WALK_LDS, CNT, IT0>(L, W, it, wf_lds_nodes);
+        wf_step_body<FEAT, WALK_LDS, CNT, IT0>(L, W, it, wf_lds_nodes, cs);
     } else {
-        wf_step_body<FEAT, WALK_GLOBAL, CNT, IT0>(L, W, it, nullptr);
+        wf_step_body<FEAT, WALK_GLOBAL, CNT, IT0>(L, W, it, nullptr, cs);
     }
 }
 
@@ -1948,8 +1968,10 @@ WfGrids<FEAT> wf_grids(int n_cu) {
 template <uint32_t FEAT>
 void wf_run_fused(const rtw_launch& L, const rtw_wf& W0, hipStream_t st, int n_cu, size_t clds, size_t lds,
                   rtw_timer* T) {
+    // (the fused steps' push cursors are static LDS on top of the dynamic sizes here: cur1 at 1024 threads, cur2 at 768)
+    constexpr size_t cur1 = RTW_WF_CURSOR_BYTES(1024u), cur2 = RTW_WF_CURSOR_BYTES(768u);
     const size_t cdyn0 = clds,
-                 cdyn = cdyn0 + L.mat_lds <= 160u * 1024u ? cdyn0 + L.mat_lds : cdyn0,
+                 cdyn = cdyn0 + L.mat_lds + cur1 <= 160u * 1024u ? cdyn0 + L.mat_lds : cdyn0,
                  ldyn = lds + (L.perlin_lds ? (size_t)L.n_perlin * RTW_PERLIN_BYTES : 0) +
                         ((FEAT & RTW_F_GEOM) ? L.geom_lds : 0u) + L.shade_lds,
                  tdyn = lds + ((FEAT & RTW_F_GEOM) ? L.geom_lds : 0u) + L.shade_lds,
@@ -1961,9 +1983,9 @@ void wf_run_fused(const rtw_launch& L, const rtw_wf& W0, hipStream_t st, int n_c
     // when it fits half the LDS
     const bool y4 = L.n_orders == 4;
     const int cn = L.cnode32 ? CN_F32_4 : y4 ? CN_F16_4 : CN_F16_8;
-    const uint32_t shape = clds && cn == CN_F16_4 && cdyn0 <= RTW_WF_CLDS2_MAX && L.clds_shape == 4u ? 4u : 1u;
+    const uint32_t shape = clds && cn == CN_F16_4 && cdyn0 + cur2 <= RTW_WF_CLDS2_MAX && L.clds_shape == 4u ? 4u : 1u;
     const bool two = shape == 4u;
-    const size_t cdyn2 = two && cdyn > RTW_WF_CLDS2_MAX ? cdyn0 : cdyn;  // materials only if they fit too
+    const size_t cdyn2 = two && cdyn + cur2 > RTW_WF_CLDS2_MAX ? cdyn0 : cdyn;  // materials only if they fit too
     const uint32_t cthreads = two ? 768u : 1024u;
     if constexpr ((FEAT & RTW_WF_NO_CLDS) == 0) {
         const uint64_t key = wf_key(n_cu, (uint32_t)cdyn2 | (shape << 24) | ((uint32_t)cn << 28));
@@ -2094,7 +2116,8 @@ void wf_run(const rtw_launch& L, const rtw_wf& W0, hipStream_t st, int n_cu, rtw
         // 1024-thread compact kernel would spill at its 128-VGPR cap -- C5 -20 % measured)
         if constexpr ((FEAT & (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_MOVING | RTW_F_IMAGE | RTW_F_NOISE)) == 0) {
             const size_t c = (size_t)L.n_nodes * L.n_orders * (L.cnode32 ? 32u : 16u);
-            if (L.cnodes && L.fast_box && L.wf_clds && c <= RTW_WF_CLDS_MAX) fclds = c;
+            // (the stage and the fused step's push cursors)
+            if (L.cnodes && L.fast_box && L.wf_clds && c + RTW_WF_CURSOR_BYTES(1024u) <= RTW_WF_CLDS_MAX) fclds = c;
         }
         const size_t need = (size_t)L.n_nodes * L.n_orders * 32u;
         if (!fclds && L.wf_lds && need <= RTW_WF_LDS_MAX) flds = (need + 511u) / 512u * 512u;
