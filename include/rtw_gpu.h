@@ -539,13 +539,20 @@ int rtw_scene_stats_get(rtw_ctx* ctx, rtw_scene_stats* out);
  * estimator of the same image with less noise where the lights are small.  Emission,
  * Metal and Dielectric are unchanged; there are no shadow rays.  A caller detects the
  * capability by the presence of these symbols (the ABI version and every struct are
- * those of ABI 8).  Only quads can be lights: sphere lights (cone sampling) are out of
- * scope.
+ * those of ABI 8).  Quads are sampled by area, static spheres by the cone they subtend
+ * (from inside a sphere light: every direction).  Sphere lights came after quad lights
+ * under the same ABI version: a caller detects them by trying the call, which a library
+ * without them refuses with RTW_E_INVALID.  Out of scope: lights inside instances, moving
+ * spheres, and any light in a scene of spheres alone (no quad, instance or medium: those
+ * scenes render with kernels of their own, which have no mixture-density form).
  * ------------------------------------------------------------------------- */
 #define RTW_MAX_LIGHTS 16
-/* Registers the quads that diffuse scatter samples towards. lights[k] must be a top-level
- * RTW_OBJ_QUAD of the scene's object list (not an instance member, not a medium boundary) whose
- * material is RTW_MAT_DIFFUSE_LIGHT; n <= RTW_MAX_LIGHTS. n = 0 (lights may be NULL) clears:
+/* Registers the objects that diffuse scatter samples towards. lights[k] must be a top-level
+ * RTW_OBJ_QUAD or RTW_OBJ_SPHERE of the scene's object list (not an instance member, not a
+ * medium boundary) whose material is RTW_MAT_DIFFUSE_LIGHT; a sphere must be static
+ * (is_moving == 0) with a finite radius > 0, in a scene with at least one quad, instance or
+ * medium. Quads and spheres may be mixed, no (kind, index) twice; n <= RTW_MAX_LIGHTS.
+ * n = 0 (lights may be NULL) clears:
  * the context then renders exactly as one that never had lights. Must not race a render on
  * ctx. Works on GPU and host contexts.  Anything else returns RTW_E_INVALID with a message and
  * leaves the registered lights as they were.  rtw_scene_hash covers the registered list.

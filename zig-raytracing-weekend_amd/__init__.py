@@ -5,7 +5,7 @@ Host API (mirrors the reference's Zig API names):
   scene:   SolidColor, CheckerTexture, ImageTexture, NoiseTexture, Perlin,
            Lambertian, Metal, Dielectric, DiffuseLight, Isotropic,
            Sphere.init / Sphere.initMoving, BVHTree.init -> World;
-           flatten(objs, lights="emissive") / World.set_lights: light importance sampling
+           flatten(objs, lights="emissive" | "emissive+spheres") / World.set_lights: light importance sampling
   camera:  Camera (+ init, render(state, task)), SharedStateImageWriter, Task,
            RayTraceState, start_render
   worlds:  generate_world, earth_world, two_spheres_world, two_perlin_world,

@@ -1349,8 +1349,19 @@ RTW_DHD bool needs_unit_vector(uint32_t kind) {
 // and weights the path by pdf_scatter / (0.5 pdf_light + 0.5 pdf_scatter).  Every operation below is
 // plain fp32 in one association, the same on the host and the device (no estimates, no contraction).
 // ---------------------------------------------------------------------------
-// pdf_light of direction d from o: (1/n) sum_k pk, pk = t^2 |d|^2 / (|dot(d, n_k)| / |d| * area_k) where the
-// ray (o, d) meets light k at t >= 0.001 (Quad.hit on its own: occlusion plays no part in a density), else 0
+// 1 - cos(theta_max) of a sphere light of radius r seen from squared distance dist2, q = r^2 / dist2:
+// q / (1 + sqrt(1 - q)) -- the book's 1 - sqrt(1 - q) without its cancellation (a small far light: q below
+// 2^-24 would give 0 and an infinite density) --, or 2, every direction, from inside or on the sphere (q >= 1;
+// dist2 == 0: q = inf)
+RTW_DHD float sphere_omc(float r, float dist2) {
+    const float q = RTW_DIV(r * r, dist2);
+    return q < 1.0f ? RTW_DIV(q, 1.0f + __builtin_sqrtf(1.0f - q)) : 2.0f;
+}
+
+// pdf_light of direction d from o: (1/n) sum_k pk over the lights of both kinds, where the ray (o, d) meets
+// light k at t >= 0.001 (Quad.hit / Sphere.hit on its own: occlusion plays no part in a density), else 0.
+// Quad: pk = t^2 |d|^2 / (|dot(d, n_k)| / |d| * area_k).  Sphere: pk = 1 / (2 pi (1 - cos(theta_max))), the
+// uniform density over the cone the sphere subtends.  n and every record's kind are wave-uniform.
 RTW_DHD float light_pdf(const rtw_launch& L, f3 o, f3 d) {
     Ray lr;
     lr.o = o;
@@ -1362,8 +1373,14 @@ RTW_DHD float light_pdf(const rtw_launch& L, f3 o, f3 d) {
     float sum = 0.0f;
     for (uint32_t k = 0; k < n; k++) {
         const rtw_dev_light lt = L.lights[k];
-        const rtw_dev_quad& q = L.quads[lt.quad];
         float t;
+        if (lt.kind == RTW_OBJ_SPHERE) {
+            const f3 c = ld3(lt.c);
+            if (sphere_t(c, lt.radius, lr, kTmin, kInf, t))
+                sum = sum + RTW_DIV(1.0f, (2.0f * kPi) * sphere_omc(lt.radius, length_squared(c - o)));
+            continue;
+        }
+        const rtw_dev_quad& q = L.quads[lt.quad];
         if (quad_t(q, lr, kTmin, kInf, t)) {
             const float cosine = RTW_DIV(__builtin_fabsf(dot(d, ld3(q.n))), len);
             sum = sum + RTW_DIV((t * t) * dd, cosine * lt.area);
@@ -1375,7 +1392,7 @@ RTW_DHD float light_pdf(const rtw_launch& L, f3 o, f3 d) {
 // The mixture's draws and weight for a diffuse hit whose scatter direction is `dir` and whose scatter density
 // is pdf_scatter(d).  Draw order (after the caller's randomUnitVector, which stays first and unconditional so
 // the wave-shared rejection loops and needs_unit_vector are those of the kernels without lights): s; then,
-// only if s < 0.5, the light k, then a, then b.  False: the sample lies below the horizon (pdf_scatter == 0),
+// only if s < 0.5, the light k, then a, then b (two draws for either kind of light).  False: the sample lies below the horizon (pdf_scatter == 0),
 // the path ends.  Otherwise w = pdf_scatter / (0.5 pdf_light + 0.5 pdf_scatter) <= 2 (the denominator is
 // >= 0.5 pdf_scatter > 0).
 template <bool ISO>
@@ -1387,8 +1404,23 @@ RTW_DHD bool mixture_scatter(const rtw_launch& L, const HitPrep& h, rtw_rng& rng
         k = k < n - 1u ? k : n - 1u;
         const float a = rnd(rng);
         const float b = rnd(rng);
-        const rtw_dev_quad& q = L.quads[L.lights[k].quad];
-        dir = ((ld3(q.q) + splat(a) * ld3(q.u)) + splat(b) * ld3(q.v)) - h.p;
+        const rtw_dev_light lt = L.lights[k];
+        if (lt.kind == RTW_OBJ_SPHERE) {
+            // uniform in the cone the sphere subtends: z = 1 - b (1 - cos(theta_max)) about w = unit(centre - p),
+            // in the book's orthonormal basis ("The Rest of Your Life": helper axis, v = unit(w x helper), u = w x v)
+            const f3 dc = ld3(lt.c) - h.p;
+            const float t = b * sphere_omc(lt.radius, length_squared(dc));
+            const float z = 1.0f - t;
+            const float sn = __builtin_sqrtf(t * (2.0f - t));
+            const float phi = (2.0f * kPi) * a;
+            const f3 w = unit_vector(dc);
+            const f3 v = unit_vector(cross(w, __builtin_fabsf(w.x) > 0.9f ? mk(0, 1, 0) : mk(1, 0, 0)));
+            const f3 u = cross(w, v);
+            dir = (splat(rtw_cosf(phi) * sn) * u + splat(rtw_sinf(phi) * sn) * v) + splat(z) * w;
+        } else {
+            const rtw_dev_quad& q = L.quads[lt.quad];
+            dir = ((ld3(q.q) + splat(a) * ld3(q.u)) + splat(b) * ld3(q.v)) - h.p;
+        }
     }
     float ps;
     if constexpr (ISO) {

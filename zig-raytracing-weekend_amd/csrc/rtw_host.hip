@@ -422,6 +422,7 @@ int rtw_scene_create_ex(const rtw_scene_desc* d, int device, const rtw_tuning* t
     L.n_lights = 0;  // rtw_scene_set_lights
     L.lights = nullptr;
     ctx->quads_host = geom.quads;  // what rtw_scene_set_lights validates a light against
+    ctx->spheres_host = geom.spheres;
     ctx->members_host = geom.members;
     for (const rtw_dev_medium& m : geom.media) ctx->boundaries_host.push_back(m.boundary);
     for (uint32_t i = 0; i < d->n_materials; i++) ctx->mat_kind_host.push_back(d->materials[i].kind);
@@ -594,25 +595,34 @@ int rtw_scene_set_lights(rtw_ctx* ctx, const rtw_object* lights, uint32_t n) {
     if (n && !lights) return fail(RTW_E_INVALID, "rtw_scene_set_lights: null lights");
     if (n > RTW_MAX_LIGHTS) return fail(RTW_E_INVALID, "rtw_scene_set_lights: more than RTW_MAX_LIGHTS (16) lights");
     std::vector<rtw_dev_light> rec(n);
-    char msg[200];
+    char msg[240];
     for (uint32_t k = 0; k < n; k++) {
         const rtw_object o = lights[k];
-        if (o.kind != RTW_OBJ_QUAD) {
-            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u is not a quad (only quads can be sampled; "
-                          "sphere lights are out of scope)", k);
+        if (o.kind != RTW_OBJ_QUAD && o.kind != RTW_OBJ_SPHERE) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u is neither a quad nor a sphere (instances "
+                          "and media cannot be sampled)", k);
             return fail(RTW_E_INVALID, msg);
         }
-        if (o.index >= ctx->quads_host.size()) {
-            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u: quad index %u out of range", k, o.index);
+        const bool sph = o.kind == RTW_OBJ_SPHERE;
+        const char* what = sph ? "sphere" : "quad";
+        if (o.index >= (sph ? ctx->spheres_host.size() : ctx->quads_host.size())) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u: %s index %u out of range", k, what, o.index);
             return fail(RTW_E_INVALID, msg);
         }
-        const uint32_t ref = RTW_REF(RTW_OBJ_QUAD, o.index);
+        if (sph && !(ctx->feat & RTW_F_GEOM)) {
+            // sphere scenes walk octant copies, compact nodes, tile lists and hoisted spheres, which the
+            // RTW_F_ALL | RTW_F_PDF kernels do not
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (sphere %u): a scene of spheres alone cannot "
+                          "register lights (its kernels have no mixture-density form; out of scope)", k, o.index);
+            return fail(RTW_E_INVALID, msg);
+        }
+        const uint32_t ref = RTW_REF(o.kind, o.index);
         if (std::find(ctx->members_host.begin(), ctx->members_host.end(), ref) != ctx->members_host.end()) {
-            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (quad %u) is an instance member", k, o.index);
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (%s %u) is an instance member", k, what, o.index);
             return fail(RTW_E_INVALID, msg);
         }
         if (std::find(ctx->boundaries_host.begin(), ctx->boundaries_host.end(), ref) != ctx->boundaries_host.end()) {
-            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (quad %u) is a medium boundary", k, o.index);
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (%s %u) is a medium boundary", k, what, o.index);
             return fail(RTW_E_INVALID, msg);
         }
         bool top = false;  // a leaf of the world tree (the first ordering: object scenes keep one)
@@ -621,24 +631,43 @@ int rtw_scene_set_lights(rtw_ctx* ctx, const rtw_object* lights, uint32_t n) {
             std::memcpy(&aw, &ctx->nodes_host[i].a[3], 4);
             std::memcpy(&bz, &ctx->nodes_host[i].b[2], 4);
             std::memcpy(&bw, &ctx->nodes_host[i].b[3], 4);
-            top = (aw & RTW_LEAF_BIT) && RTW_LEAF_KIND(bw) == RTW_OBJ_QUAD && bz == o.index;
+            top = (aw & RTW_LEAF_BIT) && RTW_LEAF_KIND(bw) == o.kind && bz == o.index;
         }
         if (!top) {
-            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (quad %u) is not in the scene's object list", k,
-                          o.index);
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (%s %u) is not in the scene's object list", k,
+                          what, o.index);
             return fail(RTW_E_INVALID, msg);
         }
-        const rtw_dev_quad& q = ctx->quads_host[o.index];
-        if (ctx->mat_kind_host[q.mat] != RTW_MAT_DIFFUSE_LIGHT) {
-            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (quad %u): its material is not "
-                          "RTW_MAT_DIFFUSE_LIGHT", k, o.index);
+        const uint32_t mat = sph ? ctx->spheres_host[o.index].mat : ctx->quads_host[o.index].mat;
+        if (ctx->mat_kind_host[mat] != RTW_MAT_DIFFUSE_LIGHT) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (%s %u): its material is not "
+                          "RTW_MAT_DIFFUSE_LIGHT", k, what, o.index);
             return fail(RTW_E_INVALID, msg);
         }
         for (uint32_t j = 0; j < k; j++)
-            if (lights[j].index == o.index) {
-                std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: quad %u is listed twice", o.index);
+            if (lights[j].kind == o.kind && lights[j].index == o.index) {
+                std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: %s %u is listed twice", what, o.index);
                 return fail(RTW_E_INVALID, msg);
             }
+        rec[k] = rtw_dev_light{};
+        rec[k].kind = o.kind;
+        if (sph) {
+            const rtw_dev_sphere& s = ctx->spheres_host[o.index];
+            if (s.moving) {
+                std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (sphere %u) is a moving sphere (out of "
+                              "scope: only static spheres can be sampled)", k, o.index);
+                return fail(RTW_E_INVALID, msg);
+            }
+            if (!(s.radius > 0.0f) || !std::isfinite(s.radius)) {
+                std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (sphere %u) has no finite positive radius",
+                              k, o.index);
+                return fail(RTW_E_INVALID, msg);
+            }
+            rec[k].radius = s.radius;
+            for (int i = 0; i < 3; i++) rec[k].c[i] = s.c1[i];
+            continue;
+        }
+        const rtw_dev_quad& q = ctx->quads_host[o.index];
         // area = |cross(u, v)| (vec3.zig:31-33 cross, fp32)
         const float cx = q.u[1] * q.v[2] - q.u[2] * q.v[1], cy = q.u[2] * q.v[0] - q.u[0] * q.v[2],
                     cz = q.u[0] * q.v[1] - q.u[1] * q.v[0];

@@ -90,7 +90,8 @@ struct rtw_launch {
     uint32_t hit_bits;           // RTW_F_TREE kernels: the hit id is leaf node | member << hit_bits (else 24)
     // light importance sampling (rtw_scene_set_lights; RTW_F_PDF kernels), read through L1/L2
     uint32_t n_lights;           // 0: none registered -- the kernels without RTW_F_PDF run
-    const rtw_dev_light* lights; // n_lights records; each light's geometry is quads[lights[k].quad]
+    const rtw_dev_light* lights; // n_lights records by kind: a quad's geometry is quads[lights[k].quad], a
+                                 // sphere's centre and radius are in the record
 };
 
 #define RTW_TILE_W 16
@@ -254,12 +255,13 @@ struct rtw_ctx {
     std::vector<hipEvent_t> ev_pool;  // recycled timing events
     uint64_t scene_hash = 0;       // FNV-1a 64 of the uploaded scene image
     // light importance sampling (rtw_scene_set_lights): the registered list, what validates it (host copies
-    // of the quads, the instance member and medium boundary references, the materials' kinds) and the
+    // of the quads and spheres, the instance member and medium boundary references, the materials' kinds) and the
     // device records (GPU context: d_lights, RTW_MAX_LIGHTS records; host context: lights_rec itself)
     std::vector<rtw_object> lights;
     std::vector<rtw_dev_light> lights_rec;
     rtw_dev_light* d_lights = nullptr;
     std::vector<rtw_dev_quad> quads_host;
+    std::vector<rtw_dev_sphere> spheres_host;
     std::vector<uint32_t> members_host, boundaries_host, mat_kind_host;
     float box_pad = 0;             // absolute pad baked into the inner boxes (SAH trees), 0 = none
     float extent = 0;              // max |coordinate| over the scene's boxes

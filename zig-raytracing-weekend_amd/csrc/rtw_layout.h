@@ -60,14 +60,20 @@ struct rtw_dev_quad {
 };
 static_assert(sizeof(rtw_dev_quad) == 80, "quad record must be 80 bytes");
 
-// 8 B: a registered light (rtw_scene_set_lights).  Its q, u, v, n, d, w are the quad's own record,
-// quads[quad] -- one copy, which rides in the LDS geometry stage wherever the quads do --, beside
-// area = |cross(u, v)| (fp32, computed once on the host)
+// 32 B: a registered light (rtw_scene_set_lights), by kind (RTW_OBJ_QUAD / RTW_OBJ_SPHERE).
+// Quad: its q, u, v, n, d, w are the quad's own record, quads[quad] -- one copy, which rides in the LDS
+// geometry stage wherever the quads do --, beside area = |cross(u, v)| (fp32, computed once on the host).
+// Sphere: centre and radius inline (a world-tree sphere leaf carries its sphere inline: there is no device
+// array of top-level spheres to index).  The fields of the other kind are 0.
 struct rtw_dev_light {
+    uint32_t kind;
     uint32_t quad;
     float area;
+    float radius;
+    float c[3];
+    uint32_t _p;
 };
-static_assert(sizeof(rtw_dev_light) == 8, "light record must be 8 bytes");
+static_assert(sizeof(rtw_dev_light) == 32, "light record must be 32 bytes");
 
 // 96 B: members[first .. first+count) (RTW_REF), xf[k] = {bits(kind), a, b, c}:
 // translate (a, b, c) = offset; rotate_y a = sin, b = cos.  xf[0] innermost.

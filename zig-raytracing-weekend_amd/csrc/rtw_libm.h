@@ -12,6 +12,8 @@
 //      FreeBSD-derived logf (Lg1..Lg4).  (When the reference links a C library those two
 //      symbols may resolve to its libm instead -- parity unpinned at that boundary; the
 //      CPU restatement, oracle/rtw_oracle.c, restates the same algorithms independently.)
+//   rtw_cosf: musl cosf in the same style, for the project's own cone sampling of sphere lights
+//      (the reference has none; checked against float64 cos).
 //
 // Same fp32/fp64 operations in the same order on every target (-ffp-contract=off, IEEE
 // division and sqrt), so the device and the CPU restatement agree bit for bit.  Domain:
@@ -273,6 +275,68 @@ RTW_LIBM_FN float rtw_sinf(float x) {
     const double c = use_cos ? C1 : S1 + z * S2;
     const double r = (use_cos ? C2 : S3) + z * (use_cos ? C3 : S4);
     const float v = (float)((a + b * c) + (w * (use_cos ? z : sz)) * r);
+    return neg_out ? -v : v;
+}
+
+// cos.zig cosf (musl), for the cone sampling of sphere lights (rtw_device.h mixture_scatter; the reference
+// itself calls no cosine).  As rtw_sinf: the ranges give (y, kernel, sign) with the source's exact double
+// operations (c - x == -(x - c), x + c == x - (-c), -x - c == -(x + c)), and both kernels are one evaluation
+// with selected operands: bit-identical to the branchy source.  Same domain as rtw_sinf.
+RTW_LIBM_FN float rtw_cosf(float x) {
+    const double c1pio2 = 1 * 1.57079632679489661923, c2pio2 = 2 * 1.57079632679489661923,
+                 c3pio2 = 3 * 1.57079632679489661923, c4pio2 = 4 * 1.57079632679489661923;
+    uint32_t ix = rtw_lm_bits(x);
+    const bool sign = (ix >> 31) != 0;
+    ix &= 0x7FFFFFFFu;
+    if (ix < 0x39800000u) return 1.0f;  // |x| < 2^-12 (and +-0)
+    if (ix >= 0x7F800000u) return x - x;  // cos(inf or nan) = nan
+    if (ix >= 0x4DC90FDBu) return rtw_lm_float(0x7FC00000u);  // beyond the medium-size reduction
+    const double xd = (double)x;
+    double y;
+    bool use_sin, neg_out = false;
+    if (ix <= 0x40E231D5u) {  // |x| ~<= 9*pi/4: one subtraction of a multiple of pi/2
+        double off;
+        bool neg_in = false;
+        if (ix <= 0x3F490FDAu) {  // |x| ~<= pi/4: cos(x)
+            off = 0.0;
+            use_sin = false;
+        } else if (ix <= 0x4016CBE3u) {  // ~<= 3pi/4: sign ? sin(x + pi/2) : sin(pi/2 - x)
+            off = sign ? -c1pio2 : c1pio2;
+            use_sin = true;
+            neg_in = !sign;
+        } else if (ix <= 0x407B53D1u) {  // ~<= 5pi/4: -cos(x -+ pi)
+            off = sign ? -c2pio2 : c2pio2;
+            use_sin = false;
+            neg_out = true;
+        } else if (ix <= 0x40AFEDDFu) {  // ~<= 7pi/4: sign ? sin(-x - 3pi/2) : sin(x - 3pi/2)
+            off = sign ? -c3pio2 : c3pio2;
+            use_sin = true;
+            neg_in = sign;
+        } else {  // ~<= 9pi/4: cos(x -+ 2pi)
+            off = sign ? -c4pio2 : c4pio2;
+            use_sin = false;
+        }
+        y = (ix <= 0x3F490FDAu) ? xd : xd - off;
+        if (neg_in) y = -y;
+    } else {
+        const int n = rtw_lm_rem_pio2f(x, &y);  // 0: cos(y), 1: sin(-y), 2: -cos(y), 3: sin(y)
+        use_sin = (n & 1) != 0;
+        neg_out = (n & 3) == 2;
+        if ((n & 3) == 1) y = -y;
+    }
+    // __cosdf and __sindf as one evaluation with selected operands (rtw_sinf)
+    const double S1 = -0x15555554cbac77.0p-55, S2 = 0x111110896efbb2.0p-59, S3 = -0x1a00f9e2cae774.0p-65,
+                 S4 = 0x16cd878c3b46a7.0p-71;
+    const double C0 = -0x1ffffffd0c5e81.0p-54, C1 = 0x155553e1053a42.0p-57, C2 = -0x16c087e80f1e27.0p-62,
+                 C3 = 0x199342e0ee5069.0p-68;
+    const double z = y * y;
+    const double w = z * z;
+    const double sz = z * y;
+    const double a = use_sin ? y : 1.0 + z * C0;
+    const double b = use_sin ? sz : w;
+    const double c = use_sin ? S1 + z * S2 : C1;
+    const double r = (use_sin ? S3 : C2) + z * (use_sin ? S4 : C3);
+    const float v = (float)((a + b * c) + (w * (use_sin ? sz : z)) * r);
     return neg_out ? -v : v;
 }
 

@@ -338,8 +338,9 @@ def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None
     """world_objects -> C-ABI records.  bvh_mode: RTW_BVH_SAH (default, fastest) or
     RTW_BVH_REFERENCE (the reference's random-axis median tree, seeded by bvh_seed).
 
-    lights: the quads diffuse scatter samples towards (rtw_scene_set_lights) -- None = none,
-    "emissive" = every top-level Quad whose material is a DiffuseLight, or a list of objects
+    lights: the quads and spheres diffuse scatter samples towards (rtw_scene_set_lights) -- None = none,
+    "emissive" = every top-level Quad whose material is a DiffuseLight, "emissive+spheres" = those, then
+    every top-level static Sphere whose material is a DiffuseLight, or a list of Quad / Sphere objects
     (found by identity among everything flattened; the library validates them).
 
     Every primitive gets its own material record (and textured materials their own
@@ -454,10 +455,13 @@ def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None
         objs.append(hittable(o))
     light_refs = None
     if isinstance(lights, str):
-        if lights != "emissive":
-            raise ValueError(f"lights: None, 'emissive' or a list of objects, not {lights!r}")
+        if lights not in ("emissive", "emissive+spheres"):
+            raise ValueError(f"lights: None, 'emissive', 'emissive+spheres' or a list of objects, not {lights!r}")
         light_refs = [ref for o, ref in zip(objects, objs)
                       if isinstance(o, Quad) and o.mat.kind == _abi.RTW_MAT_DIFFUSE_LIGHT]
+        if lights == "emissive+spheres":
+            light_refs += [ref for o, ref in zip(objects, objs)
+                           if isinstance(o, Sphere) and not o.is_moving and o.mat.kind == _abi.RTW_MAT_DIFFUSE_LIGHT]
     elif lights is not None:
         light_refs = []
         for o in lights:
@@ -521,8 +525,8 @@ class World:
                 raise
 
     def set_lights(self, lights) -> None:
-        """rtw_scene_set_lights: the quads diffuse scatter samples towards -- an OBJECT_DT array, (kind, index)
-        pairs, or None / empty to clear (the world then renders exactly as one never given lights).  Must not
+        """rtw_scene_set_lights: the quads and spheres diffuse scatter samples towards -- an OBJECT_DT array,
+        (kind, index) pairs, or None / empty to clear (the world then renders exactly as one never given lights).  Must not
         race a render on this world."""
         recs = np.zeros(0, _abi.OBJECT_DT) if lights is None else np.ascontiguousarray(
             lights if isinstance(lights, np.ndarray) and lights.dtype == _abi.OBJECT_DT
