@@ -112,12 +112,23 @@ typedef struct rtw_perlin {
 
 /* Quad.init (src/objects.zig:193-210): corner q, edges u, v.  The library derives
  * normal = unitVector(cross(u, v)), d = dot(normal, q), w = n / dot(n, n) and the
- * box fromPoints(q, q + u + v).pad() exactly as Quad.init does.  48 bytes. */
+ * box fromPoints(q, q + u + v).pad() exactly as Quad.init does.  48 bytes.
+ * shape (formerly padding, which every caller passed as 0): the interior test on the plane
+ * coordinates (alpha, beta) of the hit point.  RTW_QUAD_PARALLELOGRAM: 0 <= alpha, beta <= 1,
+ * Quad.hit.  RTW_QUAD_TRIANGLE: also alpha + beta <= 1 -- the triangle q, q + u, q + v, the book's
+ * first "additional 2D primitive"; same plane, normal, front face and (u, v) = (alpha, beta) as the
+ * quad; its box is that of its three vertices, padded as Quad.init pads.  Any other value is
+ * refused by rtw_scene_create*.  A library that knows triangles exports rtw_debug_quad_hit (the
+ * ABI version and every struct are those of ABI 8). */
+enum rtw_quad_shape {
+    RTW_QUAD_PARALLELOGRAM = 0,
+    RTW_QUAD_TRIANGLE = 1
+};
 typedef struct rtw_quad {
     float q[3];
     uint32_t material;
     float u[3];
-    uint32_t _p0;
+    uint32_t shape;            /* rtw_quad_shape */
     float v[3];
     uint32_t _p1;
 } rtw_quad;
@@ -539,7 +550,8 @@ int rtw_scene_stats_get(rtw_ctx* ctx, rtw_scene_stats* out);
  * estimator of the same image with less noise where the lights are small.  Emission,
  * Metal and Dielectric are unchanged; there are no shadow rays.  A caller detects the
  * capability by the presence of these symbols (the ABI version and every struct are
- * those of ABI 8).  Quads are sampled by area, static spheres by the cone they subtend
+ * those of ABI 8).  Quads are sampled by area (a triangle light, rtw_quad.shape, by folding the
+ * same two draws across its diagonal, with the density over half the area), static spheres by the cone they subtend
  * (from inside a sphere light: every direction).  Sphere lights came after quad lights
  * under the same ABI version: a caller detects them by trying the call, which a library
  * without them refuses with RTW_E_INVALID.  Out of scope: lights inside instances, moving
@@ -589,6 +601,13 @@ int rtw_debug_sphere_filter(uint32_t n, const float* a, const float* half_b, con
  * fresh[i] + j.  rebase[i] is what the lane with j = 0 adds to the cursor so that it continues in the fresh block. */
 int rtw_debug_push_cursor(uint32_t n, const uint32_t* blk, const uint32_t* old, const uint32_t* fresh,
                           uint32_t* slot, uint32_t* over, uint32_t* rebase);
+/* Host-only (its presence is how a caller detects triangle support, rtw_quad.shape): Quad.init's derivation
+ * (the scene builder's) and Quad.hit's interval, plane and interior tests (quad_t, the code every kernel runs) for
+ * n (record, ray) pairs: record quads[i] against the ray origins[3 i ..] + t dirs[3 i ..] on the closed interval
+ * [tmin[i], tmax[i]].  hit[i] = 1 with t[i] and alpha_beta[2 i ..] = the hit record's (u, v), else 0 with both
+ * left as they were.  A shape other than RTW_QUAD_* returns RTW_E_INVALID naming the record. */
+int rtw_debug_quad_hit(uint32_t n, const rtw_quad* quads, const float* origins, const float* dirs, const float* tmin,
+                       const float* tmax, uint8_t* hit, float* t, float* alpha_beta);
 /* GPU contexts, after a wavefront render: the stripe capacity (slots) of its last batch and the 3 x 256 stripe
  * counters (slots used per output stripe, of the last iterations' queues; a set already reset reads 0).  No
  * counter may exceed the capacity: the queues are not bound-checked on the device. */

@@ -48,6 +48,17 @@ PERLIN_DT = np.dtype([("ranvec", "<f4", (256, 3)), ("perm_x", "<u2", 256), ("per
 NODE_DT = np.dtype([("a", "<f4", 4), ("b", "<f4", 4)])
 QUAD_DT = np.dtype([("q", "<f4", 3), ("material", "<u4"), ("u", "<f4", 3), ("_p0", "<u4"), ("v", "<f4", 3),
                     ("_p1", "<u4")])
+# rtw_quad.shape travels in the word numpy calls "_p0" (the field keeps the name it had as padding: records are
+# exchanged by field name with code that predates triangles); read and write it through quad_shape()
+RTW_QUAD_PARALLELOGRAM, RTW_QUAD_TRIANGLE = 0, 1
+QUAD_SHAPE = "_p0"
+
+
+def quad_shape(quads: np.ndarray) -> np.ndarray:
+    """rtw_quad.shape of QUAD_DT records (a writable view): RTW_QUAD_PARALLELOGRAM or RTW_QUAD_TRIANGLE."""
+    return quads[QUAD_SHAPE]
+
+
 OBJECT_DT = np.dtype([("kind", "<u4"), ("index", "<u4")])
 XF_DT = np.dtype([("kind", "<u4"), ("v", "<f4", 3)])
 RTW_MAX_XF = 3
@@ -221,6 +232,8 @@ SIGNATURES = {
                                    C.c_void_p]),
     "rtw_debug_push_cursor": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "rtw_debug_quad_hit": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
     "rtw_debug_stripe_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
 }
 

@@ -116,30 +116,24 @@ public:
         for (uint32_t i = 0; i < d.n_quads; i++) {
             const rtw_quad& q = d.quads[i];
             if (q.material >= d.n_materials) return RTW_E_INVALID;
-            rtw_dev_quad& o = g_.quads[i];
-            float n[3], nn[3];
-            n[0] = q.u[1] * q.v[2] - q.u[2] * q.v[1];
-            n[1] = q.u[2] * q.v[0] - q.u[0] * q.v[2];
-            n[2] = q.u[0] * q.v[1] - q.u[1] * q.v[0];
-            const float len = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-            for (int k = 0; k < 3; k++) nn[k] = n[k] / len;
-            const float nd = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
-            o.d = nn[0] * q.q[0] + nn[1] * q.q[1] + nn[2] * q.q[2];
-            float far[3];
+            if (q.shape > RTW_QUAD_TRIANGLE) return RTW_E_INVALID;  // (rtw_scene_create_ex names the quad)
+            rtw_quad_init(q, g_.quads[i]);
+            float far[3], qu[3], qv[3];
             for (int k = 0; k < 3; k++) {
-                o.q[k] = q.q[k];
-                o.n[k] = nn[k];
-                o.u[k] = q.u[k];
-                o.v[k] = q.v[k];
-                o.w[k] = n[k] / nd;
                 far[k] = (q.q[k] + q.u[k]) + q.v[k];
+                qu[k] = q.q[k] + q.u[k];
+                qv[k] = q.q[k] + q.v[k];
             }
-            o.mat = q.material;
+            if (q.shape == RTW_QUAD_TRIANGLE) {
+                // a triangle: the box of its three vertices q, q + u, q + v, padded as Quad.init pads (Aabb.pad) --
+                // a true bound (qtrue_ too), and half the four-corner box's area for the SAH wherever u, v are
+                // not axis-aligned
+                qbox_[i] = qtrue_[i] = box_pad(box_union(box_from_points(q.q, qu), box_from_points(q.q, qv)));
+                continue;
+            }
             qbox_[i] = box_pad(box_from_points(q.q, far));
             // the reference's box spans one diagonal only (objects.zig:210): a quad whose u, v are not
             // axis-aligned can reach outside it.  qtrue_: the box of all four corners.
-            float qu[3], qv[3];
-            for (int k = 0; k < 3; k++) { qu[k] = q.q[k] + q.u[k]; qv[k] = q.q[k] + q.v[k]; }
             qtrue_[i] = box_union(box_from_points(q.q, far), box_from_points(qu, qv));
             for (int k = 0; k < 3; k++)
                 if (qtrue_[i].mn[k] < qbox_[i].mn[k] || qtrue_[i].mx[k] > qbox_[i].mx[k]) loose_ = true;

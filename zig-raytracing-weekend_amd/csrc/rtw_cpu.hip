@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdio>
 #include <thread>
 #include <vector>
 
@@ -96,6 +97,44 @@ extern "C" int rtw_debug_sphere_filter(uint32_t n, const float* a, const float* 
             }
         }
         accept[i] = ok ? 1 : 0;
+    }
+    return RTW_OK;
+}
+
+// Host-only test hook (include/rtw_gpu.h), and the symbol a caller detects triangles by: Quad.init's derivation
+// (rtw_quad_init, the scene builder's) and quad_t / quad_prep -- the device's code, the same fp32 operations --
+// for n (record, ray) pairs
+namespace {
+// (inside the namespace of rtw_device.h: at file scope its quad_t meets <sys/types.h>'s)
+bool debug_quad_t(const rtw_dev_quad& q, const Ray& r, float tmin, float tmax, float& t) {
+    return quad_t(q, r, tmin, tmax, t);
+}
+}  // namespace
+extern "C" int rtw_debug_quad_hit(uint32_t n, const rtw_quad* quads, const float* origins, const float* dirs,
+                                  const float* tmin, const float* tmax, uint8_t* hit, float* t, float* alpha_beta) {
+    if (n && (!quads || !origins || !dirs || !tmin || !tmax || !hit || !t || !alpha_beta)) return RTW_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        if (quads[i].shape > RTW_QUAD_TRIANGLE) {
+            char msg[96];
+            std::snprintf(msg, sizeof msg, "rtw_debug_quad_hit: quad %u: unknown shape %u", i, quads[i].shape);
+            rtw_set_error(msg);
+            return RTW_E_INVALID;
+        }
+        rtw_dev_quad q;
+        rtw_quad_init(quads[i], q);
+        Ray r;
+        r.o = ld3(origins + 3 * (size_t)i);
+        r.d = ld3(dirs + 3 * (size_t)i);
+        r.time = 0.0f;
+        float tt;
+        hit[i] = debug_quad_t(q, r, tmin[i], tmax[i], tt) ? 1 : 0;
+        if (hit[i]) {
+            HitPrep h;
+            quad_prep(q, r, tt, h);
+            t[i] = tt;
+            alpha_beta[2 * (size_t)i] = h.uv.u;
+            alpha_beta[2 * (size_t)i + 1] = h.uv.v;
+        }
     }
     return RTW_OK;
 }

@@ -470,7 +470,7 @@ RTW_DHD f3 member_sphere_center(const rtw_launch& L, const rtw_dev_sphere& s, ui
     return c;
 }
 
-// Quad.hit t only (objects.zig:222-255), closed interval [tmin, tmax]
+// Quad.hit t only (objects.zig:222-255), closed interval [tmin, tmax]; parallelograms and triangles (rtw_quad.shape)
 #if defined(RTW_ABLATE_QUAD2) && defined(__HIP_DEVICE_COMPILE__)
 RTW_DHD bool quad_t_once(const rtw_dev_quad& q, const Ray& r, float tmin, float tmax, float& t);
 RTW_DHD bool quad_t(const rtw_dev_quad& q, const Ray& r, float tmin, float tmax, float& t) {
@@ -496,6 +496,10 @@ RTW_DHD bool quad_t(const rtw_dev_quad& q, const Ray& r, float tmin, float tmax,
     const float alpha = dot(w, cross(planar, ld3(q.v)));
     const float beta = dot(w, cross(ld3(q.u), planar));
     if ((alpha < 0) || (1 < alpha) || (beta < 0) || (1 < beta)) return false;
+    // the shape bit (rtw_layout.h) rides in the word after n, in the 16-B load quad_t begins with: a triangle
+    // also ends at the edge alpha + beta = 1, inclusive like the others (both comparisons are evaluated: no
+    // per-shape branch)
+    if (((int32_t)q.mat < 0) & (alpha + beta > 1.0f)) return false;
     t = tt;
     return true;
 }
@@ -1233,7 +1237,7 @@ RTW_DHD HitPrep object_prep(const rtw_launch& L, const Ray& r, uint32_t kind, ui
     if (kind == RTW_OBJ_QUAD) {
         const rtw_dev_quad q = L.quads[idx];
         quad_prep(q, r, t, h);
-        h.m = L.mats[q.mat];
+        h.m = L.mats[RTW_QUAD_MAT(q.mat)];
         return h;
     }
     if (kind == RTW_OBJ_INSTANCE) {
@@ -1256,7 +1260,7 @@ RTW_DHD HitPrep object_prep(const rtw_launch& L, const Ray& r, uint32_t kind, ui
         } else {
             const rtw_dev_quad q = L.quads[mi];
             quad_prep(q, ro, t, h);
-            mat = q.mat;
+            mat = RTW_QUAD_MAT(q.mat);
         }
         inst_to_world(in, h.p, h.normal);
         h.m = L.mats[mat];
@@ -1288,11 +1292,11 @@ RTW_DHD uint32_t hit_material_kind(const float4* __restrict__ nodes, const rtw_l
     if constexpr ((FEAT & RTW_F_GEOM) != 0) {
         const uint32_t kind = RTW_LEAF_KIND(fbits(B.w)), idx = fbits(B.z);
         if (kind == RTW_OBJ_QUAD) {
-            mat = L.quads[idx].mat;
+            mat = RTW_QUAD_MAT(L.quads[idx].mat);
         } else if (kind == RTW_OBJ_INSTANCE) {
             const uint32_t ref = L.members[L.insts[idx].first + ((uint32_t)hit >> nbits)];
             const uint32_t mi = RTW_REF_INDEX(ref);
-            mat = RTW_REF_KIND(ref) == RTW_OBJ_SPHERE ? L.sph[mi].mat : L.quads[mi].mat;
+            mat = RTW_REF_KIND(ref) == RTW_OBJ_SPHERE ? L.sph[mi].mat : RTW_QUAD_MAT(L.quads[mi].mat);
         } else if (kind != RTW_OBJ_SPHERE) {
             mat = L.media[idx].mat;
         }
@@ -1360,7 +1364,7 @@ RTW_DHD float sphere_omc(float r, float dist2) {
 
 // pdf_light of direction d from o: (1/n) sum_k pk over the lights of both kinds, where the ray (o, d) meets
 // light k at t >= 0.001 (Quad.hit / Sphere.hit on its own: occlusion plays no part in a density), else 0.
-// Quad: pk = t^2 |d|^2 / (|dot(d, n_k)| / |d| * area_k).  Sphere: pk = 1 / (2 pi (1 - cos(theta_max))), the
+// Quad: pk = t^2 |d|^2 / (|dot(d, n_k)| / |d| * area_k) (a triangle: its own interior test and area).  Sphere: pk = 1 / (2 pi (1 - cos(theta_max))), the
 // uniform density over the cone the sphere subtends.  n and every record's kind are wave-uniform.
 RTW_DHD float light_pdf(const rtw_launch& L, f3 o, f3 d) {
     Ray lr;
@@ -1419,7 +1423,14 @@ RTW_DHD bool mixture_scatter(const rtw_launch& L, const HitPrep& h, rtw_rng& rng
             dir = (splat(rtw_cosf(phi) * sn) * u + splat(rtw_sinf(phi) * sn) * v) + splat(z) * w;
         } else {
             const rtw_dev_quad& q = L.quads[lt.quad];
-            dir = ((ld3(q.q) + splat(a) * ld3(q.u)) + splat(b) * ld3(q.v)) - h.p;
+            // a triangle (RTW_QUAD_TRI_BIT): the two draws folded across the edge alpha + beta = 1 -- a uniform point of
+            // it from the same two draws
+            float fa = a, fb = b;
+            if (((int32_t)q.mat < 0) & (a + b > 1.0f)) {
+                fa = 1.0f - a;
+                fb = 1.0f - b;
+            }
+            dir = ((ld3(q.q) + splat(fa) * ld3(q.u)) + splat(fb) * ld3(q.v)) - h.p;
         }
     }
     float ps;

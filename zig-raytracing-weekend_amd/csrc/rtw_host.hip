@@ -208,6 +208,13 @@ int rtw_scene_create_ex(const rtw_scene_desc* d, int device, const rtw_tuning* t
         if (t.kind == RTW_TEX_IMAGE && t.image >= d->n_images) return fail(RTW_E_INVALID, "texture image index out of range");
         if (t.kind == RTW_TEX_NOISE && t.perlin >= d->n_perlins) return fail(RTW_E_INVALID, "texture perlin index out of range");
     }
+    for (uint32_t i = 0; d->quads && i < d->n_quads; i++)
+        if (d->quads[i].shape > RTW_QUAD_TRIANGLE) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "quad %u: unknown shape %u (RTW_QUAD_PARALLELOGRAM = 0 or RTW_QUAD_TRIANGLE = 1)",
+                          i, d->quads[i].shape);
+            return fail(RTW_E_INVALID, msg);
+        }
     for (uint32_t i = 0; i < d->n_images; i++) {
         const rtw_image& im = d->images[i];
         if (im.width && im.height && (!im.data || im.bytes_per_row < 4 * im.width))
@@ -638,7 +645,7 @@ int rtw_scene_set_lights(rtw_ctx* ctx, const rtw_object* lights, uint32_t n) {
                           what, o.index);
             return fail(RTW_E_INVALID, msg);
         }
-        const uint32_t mat = sph ? ctx->spheres_host[o.index].mat : ctx->quads_host[o.index].mat;
+        const uint32_t mat = sph ? ctx->spheres_host[o.index].mat : RTW_QUAD_MAT(ctx->quads_host[o.index].mat);
         if (ctx->mat_kind_host[mat] != RTW_MAT_DIFFUSE_LIGHT) {
             std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (%s %u): its material is not "
                           "RTW_MAT_DIFFUSE_LIGHT", k, what, o.index);
@@ -668,10 +675,11 @@ int rtw_scene_set_lights(rtw_ctx* ctx, const rtw_object* lights, uint32_t n) {
             continue;
         }
         const rtw_dev_quad& q = ctx->quads_host[o.index];
-        // area = |cross(u, v)| (vec3.zig:31-33 cross, fp32)
+        // area = |cross(u, v)| (vec3.zig:31-33 cross, fp32); a triangle's (RTW_QUAD_TRI_BIT, rtw_layout.h): half of it
         const float cx = q.u[1] * q.v[2] - q.u[2] * q.v[1], cy = q.u[2] * q.v[0] - q.u[0] * q.v[2],
                     cz = q.u[0] * q.v[1] - q.u[1] * q.v[0];
-        const float area = std::sqrt(cx * cx + cy * cy + cz * cz);
+        const float par = std::sqrt(cx * cx + cy * cy + cz * cz);
+        const float area = (q.mat & RTW_QUAD_TRI_BIT) ? par / 2.0f : par;
         if (!(area > 0.0f) || !std::isfinite(area)) {
             std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (quad %u) has no area", k, o.index);
             return fail(RTW_E_INVALID, msg);

@@ -190,6 +190,29 @@ struct rtw_geometry {
     std::vector<rtw_node> inodes;            // the instance trees (rtw_dev_instance.tree = first node + 1)
 };
 
+// Quad.init (objects.zig:201-210): the device record of a quad description -- normal = unitVector(cross(u, v)),
+// d = dot(normal, q), w = n / dot(n, n); the shape is the top bit of mat (rtw_layout.h).  One definition for the
+// scene builder (rtw_bvh.hip) and rtw_debug_quad_hit (rtw_cpu.hip).
+inline void rtw_quad_init(const rtw_quad& q, rtw_dev_quad& o) {
+    float n[3], nn[3];
+    n[0] = q.u[1] * q.v[2] - q.u[2] * q.v[1];
+    n[1] = q.u[2] * q.v[0] - q.u[0] * q.v[2];
+    n[2] = q.u[0] * q.v[1] - q.u[1] * q.v[0];
+    const float len = __builtin_sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    for (int k = 0; k < 3; k++) nn[k] = n[k] / len;
+    const float nd = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+    o = rtw_dev_quad{};
+    o.d = nn[0] * q.q[0] + nn[1] * q.q[1] + nn[2] * q.q[2];
+    for (int k = 0; k < 3; k++) {
+        o.q[k] = q.q[k];
+        o.n[k] = nn[k];
+        o.u[k] = q.u[k];
+        o.v[k] = q.v[k];
+        o.w[k] = n[k] / nd;
+    }
+    o.mat = q.material | (q.shape == RTW_QUAD_TRIANGLE ? RTW_QUAD_TRI_BIT : 0u);
+}
+
 // Validates the object graph, derives the geometry records and builds the BVH
 // over world_objects.  box_pad/extent (out, may be null): SAH trees pad every
 // inner box by extent * 2^-19 so the FMA slab test (box_next) stays conservative.

@@ -48,7 +48,11 @@ struct rtw_dev_sphere {
 };
 static_assert(sizeof(rtw_dev_sphere) == 32, "sphere record must be 32 bytes");
 
-// 80 B: Quad.init derived fields (objects.zig:201-210)
+// 80 B: Quad.init derived fields (objects.zig:201-210).  u[3] = v[3] = w[3] = 0.  mat = the material index |
+// RTW_QUAD_TRI_BIT for the triangle q, q + u, q + v (rtw_quad.shape): a parallelogram's word is the index it always
+// was.  The word shares its 16 bytes with n, the first thing quad_t loads: the shape costs no load of its own.
+#define RTW_QUAD_TRI_BIT 0x80000000u
+#define RTW_QUAD_MAT(m) ((m) & 0x7FFFFFFFu)
 struct rtw_dev_quad {
     float q[3];
     float d;
@@ -62,7 +66,8 @@ static_assert(sizeof(rtw_dev_quad) == 80, "quad record must be 80 bytes");
 
 // 32 B: a registered light (rtw_scene_set_lights), by kind (RTW_OBJ_QUAD / RTW_OBJ_SPHERE).
 // Quad: its q, u, v, n, d, w are the quad's own record, quads[quad] -- one copy, which rides in the LDS
-// geometry stage wherever the quads do --, beside area = |cross(u, v)| (fp32, computed once on the host).
+// geometry stage wherever the quads do --, beside area = |cross(u, v)| (fp32, computed once on the host; a
+// triangle's: half of it).
 // Sphere: centre and radius inline (a world-tree sphere leaf carries its sphere inline: there is no device
 // array of top-level spheres to index).  The fields of the other kind are 0.
 struct rtw_dev_light {

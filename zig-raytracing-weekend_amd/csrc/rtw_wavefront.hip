@@ -59,8 +59,8 @@
 #ifndef RTW_WPE_TAIL_LDS  // object classes with media / textures / motion; the plain one RTW_WPE_TAIL_LDS_OBJ
 #define RTW_WPE_TAIL_LDS 5
 #endif
-#ifndef RTW_WPE_TAIL_LDS_OBJ
-#define RTW_WPE_TAIL_LDS_OBJ 6
+#ifndef RTW_WPE_TAIL_LDS_OBJ  // 5 since quads carry a shape: at 6 (80 VGPRs) the shape test's live word took the
+#define RTW_WPE_TAIL_LDS_OBJ 5  // spill from 144 to 188 B and Cornell's tail from 20.2 to 33.5 ms; at 5: 21.9, at 4: 24.6
 #endif
 // the split trace / shade targets apply to the untextured static sphere classes they were measured on (C4);
 // the other classes' split kernels (large object or textured trees: 100-200 VGPRs) keep no target
@@ -68,7 +68,7 @@ template <uint32_t FEAT>
 constexpr int wf_split_wpe(int w) { return (FEAT & ~RTW_F_CHECKER) == 0 ? w : 1; }
 template <uint32_t FEAT>
 constexpr int wf_tail_lds_wpe() {
-    // the object class without media, textures or motion (Cornell) at 6; the media class (Cornell smoke, 126 VGPRs)
+    // the object class without media, textures or motion (Cornell) and the media class (Cornell smoke, 126 VGPRs)
     // at 5; every other class keeps no target -- simple_light's all-features tail at 5 or 6 waves spilled 184 B and
     // lost 27 % of its tail time (profiles/r6_waves/o/, q/)
     constexpr uint32_t tex = RTW_F_IMAGE | RTW_F_NOISE | RTW_F_MOVING;

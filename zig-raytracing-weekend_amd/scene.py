@@ -7,7 +7,8 @@ Reference types (all by value in Zig) and their mirrors here:
 * ``Material`` union (src/material.zig:11-30): ``Lambertian``, ``Metal``,
   ``Dielectric``, ``DiffuseLight``, ``Isotropic``
 * ``Sphere`` (src/objects.zig:68-149): ``Sphere.init`` / ``Sphere.initMoving``
-* ``Quad`` (src/objects.zig:193-262), ``HittableList`` (:264-290), ``Translate``
+* ``Quad`` (src/objects.zig:193-262; ``Triangle``, ``Mesh`` and ``load_obj``: the same record with the
+  triangle's interior test), ``HittableList`` (:264-290), ``Translate``
   (:292-331), ``RotateY`` (:333-443), ``ConstantMedium`` (:445-508) and
   ``createBox`` (:510-532)
 * ``BVHTree`` (src/bvh.zig:17-104): ``BVHTree.init(objects, start, end)`` --
@@ -204,20 +205,43 @@ class Sphere:
 
 @dataclass(eq=False)
 class Quad:
-    """Quad.init (objects.zig:201-210); the library derives normal, d, w and the box."""
+    """Quad.init (objects.zig:201-210); the library derives normal, d, w and the box.
+
+    shape: RTW_QUAD_PARALLELOGRAM, or RTW_QUAD_TRIANGLE -- the triangle q, q + u, q + v (``Triangle.init``)."""
     q: np.ndarray
     u: np.ndarray
     v: np.ndarray
     mat: Material
+    shape: int = _abi.RTW_QUAD_PARALLELOGRAM
 
     @staticmethod
     def init(q, u, v, mat: Material) -> "Quad":
         return Quad(_v3(q), _v3(u), _v3(v), mat)
 
 
+class Triangle:
+    """The book's first "additional 2D primitive": a Quad record with another interior test (alpha + beta <= 1,
+    inclusive like the quad's edges).  Plane, normal (cross(b - a, c - a)), front face and (u, v) = (alpha, beta)
+    are the quad's; the box is that of the three vertices."""
+
+    @staticmethod
+    def init(a, b, c, mat: Material) -> Quad:
+        a = _v3(a)
+        return Quad(a, _v3(b) - a, _v3(c) - a, mat, _abi.RTW_QUAD_TRIANGLE)
+
+
+def quad_triangles(quad: Quad) -> List[Quad]:
+    """The two triangles (q, u, v) and (q + u + v, -u, -v) that tile a parallelogram (same plane and normal)."""
+    if quad.shape != _abi.RTW_QUAD_PARALLELOGRAM:
+        raise ValueError("not a parallelogram")
+    far = (quad.q + quad.u) + quad.v
+    return [Quad(quad.q.copy(), quad.u.copy(), quad.v.copy(), quad.mat, _abi.RTW_QUAD_TRIANGLE),
+            Quad(far, -quad.u, -quad.v, quad.mat, _abi.RTW_QUAD_TRIANGLE)]
+
+
 @dataclass(eq=False)
 class HittableList:
-    """objects.zig:264-290 (members: Spheres / Quads).
+    """objects.zig:264-290 (members: Spheres / Quads / Triangles).
 
     bvh: under a transform the library walks a private BVH over the members (``Hittable{.tree}`` in the
     reference) instead of testing them in turn -- True / False, or None = when there are more than 127."""
@@ -230,6 +254,56 @@ class HittableList:
 
     def add(self, obj) -> None:
         self.objects.append(obj)
+
+
+@dataclass(eq=False)
+class Mesh(HittableList):
+    """A triangle mesh: a HittableList of ``Triangle``s over shared vertices -- bare or under Translate / RotateY
+    it is an instance (more than 127 triangles: with a private BVH, as any list; ``bvh`` as HittableList's), and
+    as such a ConstantMedium boundary.  Flat shading: no per-vertex normals or texture coordinates."""
+    vertices: np.ndarray = None   # (n, 3) f32
+    faces: np.ndarray = None      # (m, 3) vertex indices
+
+    @staticmethod
+    def init(vertices, faces, mat: Material, bvh: Optional[bool] = None) -> "Mesh":
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(faces, dtype=np.int64).reshape(-1, 3)
+        if len(f) and (f.min() < 0 or f.max() >= len(v)):
+            raise ValueError("face index out of range")
+        return Mesh([Triangle.init(v[i], v[j], v[k], mat) for i, j, k in f], bvh, v, f)
+
+
+def load_obj(path_or_text: str, mat: Material, bvh: Optional[bool] = None) -> Mesh:
+    """A Wavefront OBJ file (or its text, if the argument has a line break) as a Mesh: ``v`` and ``f`` lines only
+    -- face corners ``i``, ``i/j``, ``i/j/k`` or ``i//k`` (the vertex index is used), 1-based or negative
+    (relative to the vertices read so far), polygons as fans about their first corner.  Everything else is
+    ignored; an index out of range raises ValueError."""
+    if "\n" in path_or_text:
+        text = path_or_text
+    else:
+        with open(path_or_text) as fh:
+            text = fh.read()
+    verts, faces = [], []
+    for ln, line in enumerate(text.splitlines(), 1):
+        tok = line.split("#", 1)[0].split()
+        if not tok:
+            continue
+        if tok[0] == "v":
+            if len(tok) < 4:
+                raise ValueError(f"line {ln}: a vertex needs three coordinates")
+            verts.append([float(x) for x in tok[1:4]])
+        elif tok[0] == "f":
+            corners = []
+            for c in tok[1:]:
+                i = int(c.split("/", 1)[0])
+                k = i - 1 if i > 0 else len(verts) + i
+                if i == 0 or not 0 <= k < len(verts):
+                    raise ValueError(f"line {ln}: vertex index {i} out of range ({len(verts)} vertices so far)")
+                corners.append(k)
+            if len(corners) < 3:
+                raise ValueError(f"line {ln}: a face needs three corners")
+            faces += [(corners[0], corners[j], corners[j + 1]) for j in range(1, len(corners) - 1)]
+    return Mesh.init(np.array(verts, np.float32).reshape(-1, 3), np.array(faces, np.int64).reshape(-1, 3), mat, bvh)
 
 
 @dataclass(eq=False)
@@ -407,6 +481,7 @@ def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None
         if isinstance(o, Quad):
             rec = np.zeros((), _abi.QUAD_DT)
             rec["q"], rec["u"], rec["v"] = o.q, o.u, o.v
+            _abi.quad_shape(rec)[...] = o.shape
             rec["material"] = mat_index(o.mat)
             quads.append(rec)
             return (_abi.RTW_OBJ_QUAD, len(quads) - 1)

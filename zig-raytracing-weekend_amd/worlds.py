@@ -12,9 +12,11 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
+from . import _abi
 from .rng import DOMAIN_SCENE, Stream, f32
 from .scene import (CheckerTexture, ConstantMedium, Dielectric, DiffuseLight, HittableList, Image, ImageTexture,
-                    Lambertian, Metal, NoiseTexture, Perlin, Quad, RotateY, SolidColor, Sphere, Translate, createBox)
+                    Lambertian, Mesh, Metal, NoiseTexture, Perlin, Quad, RotateY, SolidColor, Sphere, Translate,
+                    Triangle, createBox, quad_triangles)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -213,6 +215,62 @@ def cornell_smoke() -> list:
     objs.append(ConstantMedium.initFromColor(box2, 0.01, [1, 1, 1]))
     return objs
 
+
+def icosphere(level: int, centre, radius, mat, bvh: Optional[bool] = None) -> Mesh:
+    """A sphere of 20 * 4^level triangles (generated, not loaded): the icosahedron, every triangle split in four
+    `level` times, the new vertices pushed out to the sphere.  Closed, every edge shared by two triangles, normals
+    (cross(b - a, c - a)) outward.  Vertices are computed in float64 and rounded once."""
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    verts = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t),
+             (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    verts = [np.array(v, np.float64) / np.linalg.norm(v) for v in verts]
+    faces = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2),
+             (10, 7, 6), (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11),
+             (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(level):
+        mid = {}
+
+        def midpoint(i, j):
+            key = (min(i, j), max(i, j))
+            if key not in mid:
+                m = verts[i] + verts[j]
+                verts.append(m / np.linalg.norm(m))
+                mid[key] = len(verts) - 1
+            return mid[key]
+
+        split = []
+        for a, b, c in faces:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            split += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        faces = split
+    v = np.asarray(centre, np.float64).reshape(3) + float(radius) * np.array(verts)
+    return Mesh.init(v.astype(np.float32), np.array(faces, np.int64), mat, bvh)
+
+
+def cornell_mesh(level: int = 2, analytic: bool = False) -> list:
+    """The Cornell box (camera: camera.cornell_camera) with triangles in every place a scene can hold them: the
+    ceiling light as two emissive triangles, the tall box replaced by an icosphere of 20 * 4^level triangles under
+    RotateY + Translate (level 2: 320, an instance with a private BVH), the short box by its 12 triangles (an
+    instance tested as a list), and one free-standing top-level triangle.  analytic: the icosphere's place taken by
+    the Sphere it approximates (the price of the mesh, for measurements)."""
+    walls, white = _cornell_walls([343, 554, 332], [-130, 0, 0], [0, 0, -105], [15, 15, 15])
+    objs = []
+    for q in walls:
+        objs += quad_triangles(q) if q.mat.kind == _abi.RTW_MAT_DIFFUSE_LIGHT else [q]
+    if analytic:
+        ball = HittableList.init()
+        ball.add(Sphere.init([82.5, 100, 82.5], 90, white))
+    else:
+        ball = icosphere(level, [82.5, 100, 82.5], 90, white)
+    objs.append(Translate.init(RotateY.init(ball, 15), [265, 0, 295]))
+    box = HittableList.init()
+    for side in createBox([0, 0, 0], [165, 165, 165], white).objects:
+        for tri in quad_triangles(side):
+            box.add(tri)
+    objs.append(Translate.init(RotateY.init(box, -18), [130, 0, 65]))
+    objs.append(Triangle.init([300, 10, 60], [420, 10, 90], [350, 150, 120],
+                              Lambertian.init(SolidColor.init([0.2, 0.4, 0.8]))))
+    return objs
 
 
 def next_week_world(seed: int = 0, boxes_per_side: int = 20, cluster: int = 1000,
