@@ -573,6 +573,38 @@ int rtw_scene_set_lights(rtw_ctx* ctx, const rtw_object* lights, uint32_t n);
 /* Copies the registered lights (out may be NULL to query the count; at most cap are written). */
 int rtw_scene_lights_get(rtw_ctx* ctx, rtw_object* out, uint32_t cap, uint32_t* n_out);
 
+/* ---------------------------------------------------------------------------
+ * Smooth shading and mesh UVs: per-vertex normals and texture coordinates on triangles
+ * (rtw_quad.shape == RTW_QUAD_TRIANGLE).  A caller detects the capability by the presence of
+ * these symbols (the ABI version and every struct are those of ABI 8).  With (alpha, beta) the
+ * hit's coordinates along u and v and w0 = (1 - alpha) - beta:
+ *   RTW_ATTR_NORMALS: the shading normal is unit(((w0 n0) + (alpha n1)) + (beta n2)), or the
+ *     geometric normal n where that sum vanishes, turned to n's side, then towards the ray as
+ *     the geometric normal is (front_face stays the geometric test).  Scatter uses it; emission,
+ *     the medium test and the light density keep the geometric normal.
+ *   RTW_ATTR_UVS: (u, v) = ((w0 uv0) + (alpha uv1)) + (beta uv2), instead of (alpha, beta).
+ * Plain fp32 in this association on every backend.  Out of scope: attributes on
+ * parallelograms, tangent frames, and a guard for scattered directions below the face.
+ * ------------------------------------------------------------------------- */
+enum { RTW_ATTR_NORMALS = 1u, RTW_ATTR_UVS = 2u };
+typedef struct rtw_vertex_attr {      /* 64 bytes; corners in the order q, q + u, q + v */
+    float normal[3][3];               /* need not be unit: normalised at registration */
+    float uv[3][2];
+    uint32_t flags;                   /* RTW_ATTR_* */
+} rtw_vertex_attr;
+/* Registers attrs[k] on quad quads[k] (an index into the scene's quads, wherever the triangle
+ * sits: top level, list or tree instance, medium boundary, registered light).  Replaces the
+ * registered set; n = 0 (both pointers may be NULL) clears: the context then renders exactly as
+ * one that never had attributes.  Refused with RTW_E_INVALID, the entry named in rtw_last_error
+ * and the registered set left as it was: an index out of range, a parallelogram, an index listed
+ * twice, unknown flag bits, with RTW_ATTR_NORMALS a normal that is not finite or has zero length,
+ * with RTW_ATTR_UVS a uv that is not finite.  Fields whose flag is not set are ignored (stored
+ * as 0).  Must not race a render on ctx.  Works on GPU and host contexts.  rtw_scene_hash covers
+ * the registered set; rtw_multi_create refuses contexts whose sets differ. */
+int rtw_scene_set_vertex_attrs(rtw_ctx* ctx, const uint32_t* quads, const rtw_vertex_attr* attrs, uint32_t n);
+/* Copies the registered entries, normals normalised (either output may be NULL; at most cap are written). */
+int rtw_scene_vertex_attrs_get(rtw_ctx* ctx, uint32_t* quads, rtw_vertex_attr* attrs, uint32_t cap, uint32_t* n_out);
+
 /* Copies the flattened node array (32 B per node) to host. */
 int rtw_scene_nodes(rtw_ctx* ctx, void* out, uint32_t cap, uint32_t* n_out);
 /* Copies the private BVH of instance `instance` (RTW_INST_BVH, or more than 127 members): 32 B per node, the
@@ -608,6 +640,13 @@ int rtw_debug_push_cursor(uint32_t n, const uint32_t* blk, const uint32_t* old, 
  * left as they were.  A shape other than RTW_QUAD_* returns RTW_E_INVALID naming the record. */
 int rtw_debug_quad_hit(uint32_t n, const rtw_quad* quads, const float* origins, const float* dirs, const float* tmin,
                        const float* tmax, uint8_t* hit, float* t, float* alpha_beta);
+/* Host-only: the hit record of a triangle with vertex attributes -- Quad.init's derivation, quad_prep and
+ * quad_attr, the code every kernel runs -- for n (record, attribute, ray, t) tuples: normal[3 i ..] the shading
+ * normal turned towards the ray, uv[2 i ..] the hit's (u, v), front[i] the geometric front-face test.  The
+ * attribute is taken as given, except that its normals are normalised as registration normalises them; flags = 0
+ * gives quad_prep's record.  A shape other than RTW_QUAD_* or unknown flag bits return RTW_E_INVALID. */
+int rtw_debug_quad_shade(uint32_t n, const rtw_quad* quads, const rtw_vertex_attr* attrs, const float* origins,
+                         const float* dirs, const float* t, float* normal, float* uv, uint8_t* front);
 /* GPU contexts, after a wavefront render: the stripe capacity (slots) of its last batch and the 3 x 256 stripe
  * counters (slots used per output stripe, of the last iterations' queues; a set already reset reads 0).  No
  * counter may exceed the capacity: the queues are not bound-checked on the device. */

@@ -7,6 +7,9 @@
     python tools/mesh_ab.py mesh out.json [repeats]    worlds.cornell_mesh(level 5) -- a 20 480-triangle icosphere as a
                                                        tree instance -- against the same scene with the analytic
                                                        Sphere in its place, lights off and on, with per-kernel times.
+    python tools/mesh_ab.py smooth out.json [repeats]  the price of per-vertex normals (DESIGN.md §Smooth shading and mesh
+                                                       UVs): worlds.cornell_mesh(5, smooth=True) -- the attribute
+                                                       kernels -- against cornell_mesh(5), lights off and on.
     python tools/mesh_ab.py leaks out.json [--host-only]  the camera inside a closed emissive level-2 icosphere, depth 1,
                                                        64 x 64 x 64 spp: samples that escape (device 0 and the host).
 
@@ -54,6 +57,7 @@ def time_arms(arms, cam):
         rec[k] = {"ms": ms[k], "median_ms": med, "msamples_per_s": cam.size * SPP / med / 1e3,
                   "finite": bool(torch.isfinite(img[k]).all()), "mean_rgb": (img[k][:, :3].mean(0) / SPP).tolist(),
                   "lights": w.lights().tolist(), "stats": w.stats(),
+                  "vertex_attrs": 0 if w.arrays.vertex_attrs is None else int(len(w.arrays.vertex_attrs[0])),
                   "kernel_ms": {n: tm.ms[i] for i, n in enumerate(rtw._abi.RTW_K_NAMES) if tm.launches[i]}}
         w.close()
     return rec
@@ -92,6 +96,8 @@ else:
     cam = rtw.cornell_camera(W, SPP, DEPTH).init()
     if MODE == "quads":
         scenes = {"cornell": rtw.worlds.cornell_box(), "cornell_smoke": rtw.worlds.cornell_smoke()}
+    elif MODE == "smooth":
+        scenes = {"mesh_level5_smooth": rtw.worlds.cornell_mesh(5, smooth=True), "mesh_level5_flat": rtw.worlds.cornell_mesh(5)}
     else:
         scenes = {"mesh_level5": rtw.worlds.cornell_mesh(5), "analytic_sphere": rtw.worlds.cornell_mesh(5, analytic=True)}
     for name, objs in scenes.items():

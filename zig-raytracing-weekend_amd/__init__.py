@@ -7,6 +7,8 @@ Host API (mirrors the reference's Zig API names):
            Sphere.init / Sphere.initMoving, Quad.init, Triangle.init, Mesh.init, load_obj,
            BVHTree.init -> World;
            flatten(objs, lights="emissive" | "emissive+spheres") / World.set_lights: light importance sampling
+           Triangle.init(..., normals=, uvs=), Mesh.init(..., normals=, uvs=), load_obj(..., attributes=True) /
+           World.set_vertex_attrs: smooth shading and mesh UVs
   camera:  Camera (+ init, render(state, task)), SharedStateImageWriter, Task,
            RayTraceState, start_render
   worlds:  generate_world, earth_world, two_spheres_world, two_perlin_world,

@@ -60,6 +60,10 @@ def quad_shape(quads: np.ndarray) -> np.ndarray:
 
 
 OBJECT_DT = np.dtype([("kind", "<u4"), ("index", "<u4")])
+# rtw_vertex_attr (64 B): per-corner normals and uvs of a triangle, corners in the order q, q + u, q + v
+RTW_ATTR_NORMALS, RTW_ATTR_UVS = 1, 2
+VERTEX_ATTR_DT = np.dtype([("normal", "<f4", (3, 3)), ("uv", "<f4", (3, 2)), ("flags", "<u4")])
+assert VERTEX_ATTR_DT.itemsize == 64
 XF_DT = np.dtype([("kind", "<u4"), ("v", "<f4", 3)])
 RTW_MAX_XF = 3
 RTW_INST_LIST = 1
@@ -225,6 +229,8 @@ SIGNATURES = {
     "rtw_scene_stats_get": (C.c_int, [C.c_void_p, C.POINTER(RtwSceneStats)]),
     "rtw_scene_set_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "rtw_scene_lights_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "rtw_scene_set_vertex_attrs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rtw_scene_vertex_attrs_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rtw_scene_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rtw_scene_instance_nodes": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rtw_debug_rng": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
@@ -234,6 +240,8 @@ SIGNATURES = {
                                         C.c_void_p]),
     "rtw_debug_quad_hit": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    "rtw_debug_quad_shade": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
     "rtw_debug_stripe_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
 }
 

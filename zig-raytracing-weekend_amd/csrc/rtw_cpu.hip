@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
+#include <cstring>
 #include <thread>
 #include <vector>
 
@@ -29,6 +30,7 @@ int rtw_cpu_render(const rtw_launch& L, uint32_t begin, uint32_t end, float* out
     std::atomic<bool> stopped{false};
     const bool tree = (L.feat & RTW_F_TREE) != 0;  // instance trees: the instantiation the GPU kernels run
     const bool pdf = L.n_lights != 0;
+    const bool attr = L.vattrs != nullptr;  // vertex attributes registered: their instantiations (always with the trees')
     // contiguous chunks, as startRender's Tasks (main.zig:318-324); samples in order per pixel
     auto work = [&](uint32_t t) {
         const uint32_t a = begin + (uint32_t)((uint64_t)n * t / threads);
@@ -49,7 +51,10 @@ int rtw_cpu_render(const rtw_launch& L, uint32_t begin, uint32_t end, float* out
             for (uint32_t s = L.s0; s < L.s1; s++) {
                 const uint32_t px = x + L.pixel_offset, py = y + L.pixel_offset;
                 f3 c;
-                if (pdf)  // lights registered: the mixture-density instantiations
+                if (attr)
+                    c = pdf ? sample_radiance<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>(L.nodes, L, pixel, px, py, s, cnt)
+                            : sample_radiance<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR>(L.nodes, L, pixel, px, py, s, cnt);
+                else if (pdf)  // lights registered: the mixture-density instantiations
                     c = tree ? sample_radiance<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF>(L.nodes, L, pixel, px, py, s, cnt)
                              : sample_radiance<RTW_F_ALL | RTW_F_PDF>(L.nodes, L, pixel, px, py, s, cnt);
                 else
@@ -135,6 +140,50 @@ extern "C" int rtw_debug_quad_hit(uint32_t n, const rtw_quad* quads, const float
             alpha_beta[2 * (size_t)i] = h.uv.u;
             alpha_beta[2 * (size_t)i + 1] = h.uv.v;
         }
+    }
+    return RTW_OK;
+}
+
+// Host-only test hook (include/rtw_gpu.h), and the symbol a caller detects vertex attributes by: the hit record of
+// (record, attribute, ray, t) -- rtw_quad_init, quad_prep and quad_attr, the device's code, the same fp32 operations
+extern "C" int rtw_debug_quad_shade(uint32_t n, const rtw_quad* quads, const rtw_vertex_attr* attrs, const float* origins,
+                                    const float* dirs, const float* t, float* normal, float* uv, uint8_t* front) {
+    if (n && (!quads || !attrs || !origins || !dirs || !t || !normal || !uv || !front)) return RTW_E_INVALID;
+    char msg[96];
+    for (uint32_t i = 0; i < n; i++) {
+        if (quads[i].shape > RTW_QUAD_TRIANGLE) {
+            std::snprintf(msg, sizeof msg, "rtw_debug_quad_shade: quad %u: unknown shape %u", i, quads[i].shape);
+            rtw_set_error(msg);
+            return RTW_E_INVALID;
+        }
+        if (attrs[i].flags & ~(uint32_t)(RTW_ATTR_NORMALS | RTW_ATTR_UVS)) {
+            std::snprintf(msg, sizeof msg, "rtw_debug_quad_shade: attribute %u: unknown flag bits 0x%x", i, attrs[i].flags);
+            rtw_set_error(msg);
+            return RTW_E_INVALID;
+        }
+        rtw_dev_quad q;
+        rtw_quad_init(quads[i], q);
+        rtw_vertex_attr a = attrs[i];
+        if ((a.flags & RTW_ATTR_NORMALS) && !rtw_vattr_normalise(attrs[i], a)) {
+            std::snprintf(msg, sizeof msg, "rtw_debug_quad_shade: attribute %u: a normal is not finite or has zero length", i);
+            rtw_set_error(msg);
+            return RTW_E_INVALID;
+        }
+        rtw_dev_vattr va;
+        std::memcpy(&va, &a, sizeof va);
+        Ray r;
+        r.o = ld3(origins + 3 * (size_t)i);
+        r.d = ld3(dirs + 3 * (size_t)i);
+        r.time = 0.0f;
+        HitPrep h;
+        quad_prep(q, r, t[i], h);
+        quad_attr(&va, h);
+        normal[3 * (size_t)i] = h.normal.x;
+        normal[3 * (size_t)i + 1] = h.normal.y;
+        normal[3 * (size_t)i + 2] = h.normal.z;
+        uv[2 * (size_t)i] = h.uv.u;
+        uv[2 * (size_t)i + 1] = h.uv.v;
+        front[i] = h.front ? 1 : 0;
     }
     return RTW_OK;
 }

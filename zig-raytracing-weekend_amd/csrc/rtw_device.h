@@ -1230,13 +1230,45 @@ RTW_DHD void quad_prep(const rtw_dev_quad& q, const Ray& r, float t, HitPrep& h)
     h.uv.outward = n;
 }
 
+// Per-vertex attributes of a triangle (RTW_F_ATTR kernels; rtw_scene_set_vertex_attrs, DESIGN.md §smooth shading)
+// on top of quad_prep's record h: (alpha, beta) = h.uv.(u, v), the geometric unit normal n = h.uv.outward,
+// h.front the geometric front-face test.  Corner weights w0 = (1 - alpha) - beta, alpha, beta for q, q + u, q + v.
+//   RTW_ATTR_NORMALS: m = ((w0 n0) + (alpha n1)) + (beta n2); ns = unit(m), or n where |m|^2 is not above 1e-12;
+//     ns turned to n's side; h.normal = ns turned towards the ray by the geometric test.  h.uv.outward stays n.
+//   RTW_ATTR_UVS: (u, v) = ((w0 uv0) + (alpha uv1)) + (beta uv2).
+// Plain fp32 in this association, the same on the host and the device.  The record's four 16-B loads are taken
+// only under its flags word (0 for every quad without attributes).
+RTW_DHD void quad_attr(const rtw_dev_vattr* __restrict__ va, HitPrep& h) {
+    if (va->flags == 0) return;
+    const rtw_dev_vattr a = *va;
+    const float alpha = h.uv.u, beta = h.uv.v;
+    const float w0 = (1.0f - alpha) - beta;
+    if (a.flags & RTW_ATTR_NORMALS) {
+        const f3 n = h.uv.outward;
+        const f3 m = (splat(w0) * ld3(a.normal[0]) + splat(alpha) * ld3(a.normal[1])) + splat(beta) * ld3(a.normal[2]);
+        f3 ns = n;
+        if (length_squared(m) > 1e-12f) ns = unit_vector(m);
+        if (dot(ns, n) < 0) ns = -ns;
+        h.normal = h.front ? ns : -ns;
+    }
+    if (a.flags & RTW_ATTR_UVS) {
+        h.uv.u = ((w0 * a.uv[0][0]) + (alpha * a.uv[1][0])) + (beta * a.uv[2][0]);
+        h.uv.v = ((w0 * a.uv[0][1]) + (alpha * a.uv[1][1])) + (beta * a.uv[2][1]);
+    }
+}
+
 template <uint32_t FEAT>
 RTW_DHD HitPrep object_prep(const rtw_launch& L, const Ray& r, uint32_t kind, uint32_t idx,
                                             uint32_t sub, float t) {
+    static_assert((FEAT & RTW_F_ATTR) == 0 || (FEAT & (RTW_F_ALL | RTW_F_TREE)) == (RTW_F_ALL | RTW_F_TREE),
+                  "RTW_F_ATTR only on top of RTW_F_ALL | RTW_F_TREE");
     HitPrep h;
     if (kind == RTW_OBJ_QUAD) {
         const rtw_dev_quad q = L.quads[idx];
         quad_prep(q, r, t, h);
+        if constexpr ((FEAT & RTW_F_ATTR) != 0) {
+            if (L.vattrs) quad_attr(L.vattrs + idx, h);
+        }
         h.m = L.mats[RTW_QUAD_MAT(q.mat)];
         return h;
     }
@@ -1260,6 +1292,9 @@ RTW_DHD HitPrep object_prep(const rtw_launch& L, const Ray& r, uint32_t kind, ui
         } else {
             const rtw_dev_quad q = L.quads[mi];
             quad_prep(q, ro, t, h);
+            if constexpr ((FEAT & RTW_F_ATTR) != 0) {
+                if (L.vattrs) quad_attr(L.vattrs + mi, h);
+            }
             mat = RTW_QUAD_MAT(q.mat);
         }
         inst_to_world(in, h.p, h.normal);

@@ -428,6 +428,7 @@ int rtw_scene_create_ex(const rtw_scene_desc* d, int device, const rtw_tuning* t
     L.hit_bits = hit_bits;
     L.n_lights = 0;  // rtw_scene_set_lights
     L.lights = nullptr;
+    L.vattrs = nullptr;  // rtw_scene_set_vertex_attrs
     ctx->quads_host = geom.quads;  // what rtw_scene_set_lights validates a light against
     ctx->spheres_host = geom.spheres;
     ctx->members_host = geom.members;
@@ -502,7 +503,7 @@ int rtw_scene_create_ex(const rtw_scene_desc* d, int device, const rtw_tuning* t
     L.wf_clds = (tu.lds & RTW_LDS_CNODES) ? 1u : 0u;
     // compact LDS stage: gen, trace and shade of an iteration fused in one kernel
     // (the ray/hit hand-off through HBM disappears), tail on the LDS stage
-    L.wf_fuse = tu.fuse;
+    L.wf_fuse = tu.fuse & 7u;
     // Perlin tables (7 KiB each) staged in LDS by the fused step when at most 4 (noise scenes)
     L.perlin_lds = (ctx->feat & RTW_F_NOISE) && d->n_perlins <= 4 && (tu.lds & RTW_LDS_PERLIN) ? 1u : 0u;
     // materials of sphere scenes staged in LDS by the compact-LDS fused step when they fit beside the
@@ -556,6 +557,7 @@ void rtw_scene_destroy(rtw_ctx* ctx) {
     if (ctx->d_wf) (void)hipFree(ctx->d_wf);
     if (ctx->d_tl) (void)hipFree(ctx->d_tl);
     if (ctx->d_lights) (void)hipFree(ctx->d_lights);
+    if (ctx->d_vattrs) (void)hipFree(ctx->d_vattrs);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -593,7 +595,105 @@ int rtw_scene_hash(rtw_ctx* ctx, uint64_t* out) {
             mix(o.index);
         }
     }
+    // then the registered vertex attributes (none: the hash as it was): another image
+    if (!ctx->vattr_quads.empty()) {
+        auto mix = [&h](uint32_t w) {
+            for (int b = 0; b < 4; b++) h = (h ^ ((w >> (8 * b)) & 0xFFu)) * 0x100000001B3ull;
+        };
+        mix(0x52545441u);  // "ATTR"
+        mix((uint32_t)ctx->vattr_quads.size());
+        for (size_t k = 0; k < ctx->vattr_quads.size(); k++) {
+            mix(ctx->vattr_quads[k]);
+            uint32_t w[16];
+            std::memcpy(w, &ctx->vattr_set[k], sizeof w);
+            for (uint32_t x : w) mix(x);
+        }
+    }
     *out = h;
+    return RTW_OK;
+}
+
+int rtw_scene_set_vertex_attrs(rtw_ctx* ctx, const uint32_t* quads, const rtw_vertex_attr* attrs, uint32_t n) {
+    if (!ctx) return fail(RTW_E_INVALID, "null ctx");
+    if (n && (!quads || !attrs)) return fail(RTW_E_INVALID, "rtw_scene_set_vertex_attrs: null quads or attrs");
+    const size_t nq = ctx->quads_host.size();
+    std::vector<rtw_dev_vattr> rec(n ? nq : 0);  // dense, parallel to the quads: flags = 0 where none is registered
+    std::vector<rtw_vertex_attr> set(n);
+    std::vector<uint8_t> seen(n ? nq : 0, 0);
+    char msg[240];
+    for (uint32_t k = 0; k < n; k++) {
+        const uint32_t qi = quads[k];
+        if (qi >= nq) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_vertex_attrs: entry %u: quad index %u out of range", k, qi);
+            return fail(RTW_E_INVALID, msg);
+        }
+        if (!(ctx->quads_host[qi].mat & RTW_QUAD_TRI_BIT)) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_vertex_attrs: entry %u: quad %u is a parallelogram (only "
+                          "RTW_QUAD_TRIANGLE records take attributes)", k, qi);
+            return fail(RTW_E_INVALID, msg);
+        }
+        if (seen[qi]) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_vertex_attrs: entry %u: quad %u is listed twice", k, qi);
+            return fail(RTW_E_INVALID, msg);
+        }
+        seen[qi] = 1;
+        const rtw_vertex_attr& a = attrs[k];
+        if (a.flags & ~(uint32_t)(RTW_ATTR_NORMALS | RTW_ATTR_UVS)) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_vertex_attrs: entry %u (quad %u): unknown flag bits 0x%x", k, qi,
+                          a.flags);
+            return fail(RTW_E_INVALID, msg);
+        }
+        rtw_vertex_attr o{};
+        o.flags = a.flags;
+        if (a.flags & RTW_ATTR_NORMALS) {
+            if (!rtw_vattr_normalise(a, o)) {
+                std::snprintf(msg, sizeof msg, "rtw_scene_set_vertex_attrs: entry %u (quad %u): a normal is not finite or "
+                              "has zero length", k, qi);
+                return fail(RTW_E_INVALID, msg);
+            }
+        }
+        if (a.flags & RTW_ATTR_UVS) {
+            for (int c = 0; c < 3; c++)
+                for (int i = 0; i < 2; i++) {
+                    if (!std::isfinite(a.uv[c][i])) {
+                        std::snprintf(msg, sizeof msg, "rtw_scene_set_vertex_attrs: entry %u (quad %u): a uv is not finite",
+                                      k, qi);
+                        return fail(RTW_E_INVALID, msg);
+                    }
+                    o.uv[c][i] = a.uv[c][i];
+                }
+        }
+        set[k] = o;
+        static_assert(sizeof(rtw_dev_vattr) == sizeof(rtw_vertex_attr), "the device record is the public one");
+        std::memcpy(&rec[qi], &o, sizeof o);
+    }
+    const bool host = ctx->device == RTW_DEVICE_CPU;
+    if (!host) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        HIP_TRY(hipSetDevice(ctx->device));
+        // a render left on a caller's stream (RTW_RENDER_NO_SYNC) may still read the records
+        if (ctx->last_done) HIP_TRY(hipEventSynchronize(ctx->last_done));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (n && !ctx->d_vattrs) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->d_vattrs), nq * sizeof(rtw_dev_vattr)));
+        if (n) HIP_TRY(hipMemcpy(ctx->d_vattrs, rec.data(), nq * sizeof(rtw_dev_vattr), hipMemcpyHostToDevice));
+        // the persistent kernel's resident grid is its instantiation's
+        ctx->grid = rtw_persistent_grid(ctx->feat | (ctx->base.n_lights ? RTW_F_PDF : 0u) | (n ? RTW_F_ATTR : 0u),
+                                        ctx->stats.n_nodes, (int)ctx->base.waves, ctx->base.use_lds != 0);
+    }
+    ctx->vattr_quads.assign(quads, quads + n);
+    ctx->vattr_set = set;
+    ctx->vattrs_rec = rec;
+    ctx->base.vattrs = n ? (host ? ctx->vattrs_rec.data() : ctx->d_vattrs) : nullptr;
+    return RTW_OK;
+}
+
+int rtw_scene_vertex_attrs_get(rtw_ctx* ctx, uint32_t* quads, rtw_vertex_attr* attrs, uint32_t cap, uint32_t* n_out) {
+    if (!ctx) return fail(RTW_E_INVALID, "null ctx");
+    const uint32_t n = (uint32_t)ctx->vattr_quads.size();
+    if (n_out) *n_out = n;
+    const uint32_t m = cap < n ? cap : n;
+    if (quads && m) std::memcpy(quads, ctx->vattr_quads.data(), sizeof(uint32_t) * m);
+    if (attrs && m) std::memcpy(attrs, ctx->vattr_set.data(), sizeof(rtw_vertex_attr) * m);
     return RTW_OK;
 }
 
@@ -697,8 +797,8 @@ int rtw_scene_set_lights(rtw_ctx* ctx, const rtw_object* lights, uint32_t n) {
         if (n && !ctx->d_lights) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->d_lights), RTW_MAX_LIGHTS * sizeof(rtw_dev_light)));
         if (n) HIP_TRY(hipMemcpy(ctx->d_lights, rec.data(), n * sizeof(rtw_dev_light), hipMemcpyHostToDevice));
         // the persistent kernel's resident grid is its instantiation's
-        ctx->grid = rtw_persistent_grid(ctx->feat | (n ? RTW_F_PDF : 0u), ctx->stats.n_nodes, (int)ctx->base.waves,
-                                        ctx->base.use_lds != 0);
+        ctx->grid = rtw_persistent_grid(ctx->feat | (n ? RTW_F_PDF : 0u) | (ctx->base.vattrs ? RTW_F_ATTR : 0u),
+                                        ctx->stats.n_nodes, (int)ctx->base.waves, ctx->base.use_lds != 0);
     }
     ctx->lights.assign(lights, lights + n);
     ctx->lights_rec = rec;

@@ -2,6 +2,7 @@
 // (rtw_host.hip), the BVH builder (rtw_bvh.hip) and the kernels (rtw_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <condition_variable>
@@ -73,12 +74,19 @@ struct rtw_launch {
                                  // (only with fast_box; rtw_tuning.object_tree without RTW_OTREE_NO_CULL)
     uint32_t n_orders;           // 1, or 4 / 8 sign-ordered copies of the node array (SAH sphere scenes)
     uint32_t cnode32;            // 1: cnodes are the 32-B fp32-box nodes (rtw_tuning.compact_nodes 2)
-    uint32_t clds_shape;         // compact-LDS kernels of a 4-copy tree: 0 / 1 = one 1024-thread block per CU,
+    // per-vertex normals / uvs of triangles (rtw_scene_set_vertex_attrs; RTW_F_ATTR kernels), read through L1/L2.
+    // The pointer sits where two of the four dispatch knobs below were, and those four -- read by the host's
+    // launch code only, never by a kernel -- share one word: sizeof(rtw_launch) and every offset a kernel reads stay
+    // what they were.  (The kernels that call texture_value out of line keep a copy of this struct in scratch: one
+    // more pointer at its end cost each of them 16 B of scratch.)
+    const rtw_dev_vattr* vattrs; // null: none registered; else one record per quad, parallel to `quads`
+    uint32_t clds_shape : 8;     // compact-LDS kernels of a 4-copy tree: 0 / 1 = one 1024-thread block per CU,
                                  // 4 = two blocks of 768 threads (rtw_tuning.clds_shape)
-    uint32_t wf_lds;             // wavefront trace: stage the node array(s) in LDS when they fit
-    uint32_t wf_clds;            // wavefront trace: stage the compact nodes (all orders) in LDS when they fit
-    uint32_t wf_fuse;            // with the compact LDS stage: one gen+trace+shade kernel per iteration,
-                                 // bit 1: the tail walks the LDS stage too
+    uint32_t wf_lds : 8;         // wavefront trace: stage the node array(s) in LDS when they fit
+    uint32_t wf_clds : 8;        // wavefront trace: stage the compact nodes (all orders) in LDS when they fit
+    uint32_t wf_fuse : 8;        // with the compact LDS stage: one gen+trace+shade kernel per iteration,
+                                 // bit 1: the tail walks the LDS stage too (bits 0 .. 2 of rtw_tuning.fuse)
+    uint32_t _spare;
     uint32_t perlin_lds;         // fused step with the node array in LDS: Perlin tables staged in LDS too
     uint32_t mat_lds;            // compact-LDS fused step: bytes of the material array staged in LDS (0: off)
     uint32_t shade_lds;          // node-LDS kernels: bytes of materials | textures | image records (contiguous
@@ -93,6 +101,9 @@ struct rtw_launch {
     const rtw_dev_light* lights; // n_lights records by kind: a quad's geometry is quads[lights[k].quad], a
                                  // sphere's centre and radius are in the record
 };
+static_assert(sizeof(rtw_launch) == 416 && offsetof(rtw_launch, vattrs) == 360 && offsetof(rtw_launch, perlin_lds) == 376 &&
+                  offsetof(rtw_launch, inodes) == 392 && offsetof(rtw_launch, lights) == 408,
+              "rtw_launch keeps its size and the offsets its kernels read");
 
 #define RTW_TILE_W 16
 #define RTW_TILE_H 16
@@ -113,6 +124,9 @@ struct rtw_launch {
 #define RTW_F_PDF 256u      // lights are registered (rtw_launch.n_lights > 0): diffuse scatter samples the mixture
                             // density (scatter_finish); only ever set on top of RTW_F_ALL [| RTW_F_TREE], by the
                             // dispatchers (rtw_feat_of), never stored in rtw_launch.feat
+#define RTW_F_ATTR 512u     // vertex attributes are registered (rtw_launch.vattrs): a triangle's hit record takes its
+                            // shading normal and (u, v) from them (quad_attr); only ever set on top of RTW_F_ALL |
+                            // RTW_F_TREE [| RTW_F_PDF], by the dispatchers (rtw_feat_of), never stored in rtw_launch.feat
 
 // max nodes staged in LDS by the persistent kernel (48 KiB)
 #define RTW_MEGA_LDS_NODES_MAX 1536
@@ -121,8 +135,11 @@ struct rtw_kernel_info {
     int blocks_per_cu;
     int n_cu;
 };
-// the features a launch's kernels are picked by: the scene's, | RTW_F_PDF with lights registered
-inline uint32_t rtw_feat_of(const rtw_launch& L) { return L.feat | (L.n_lights ? RTW_F_PDF : 0u); }
+// the features a launch's kernels are picked by: the scene's, | RTW_F_PDF with lights registered, | RTW_F_ATTR with
+// vertex attributes registered
+inline uint32_t rtw_feat_of(const rtw_launch& L) {
+    return L.feat | (L.n_lights ? RTW_F_PDF : 0u) | (L.vattrs ? RTW_F_ATTR : 0u);
+}
 int rtw_persistent_grid(uint32_t feat, uint32_t n_nodes, int waves, bool use_lds);
 
 void rtw_launch_render(const rtw_launch& L, void* stream, int variant, int grid);
@@ -213,6 +230,20 @@ inline void rtw_quad_init(const rtw_quad& q, rtw_dev_quad& o) {
     o.mat = q.material | (q.shape == RTW_QUAD_TRIANGLE ? RTW_QUAD_TRI_BIT : 0u);
 }
 
+// The stored form of a vertex attribute's normals (rtw_scene_set_vertex_attrs and rtw_debug_quad_shade): each
+// divided by its fp32 length sqrt((x x + y y) + z z).  False: a normal is not finite or has zero length.
+inline bool rtw_vattr_normalise(const rtw_vertex_attr& a, rtw_vertex_attr& o) {
+    for (int c = 0; c < 3; c++) {
+        const float x = a.normal[c][0], y = a.normal[c][1], z = a.normal[c][2];
+        const float len = __builtin_sqrtf(x * x + y * y + z * z);
+        if (!(len > 0.0f) || !(len <= 3.4028234e38f)) return false;
+        o.normal[c][0] = x / len;
+        o.normal[c][1] = y / len;
+        o.normal[c][2] = z / len;
+    }
+    return true;
+}
+
 // Validates the object graph, derives the geometry records and builds the BVH
 // over world_objects.  box_pad/extent (out, may be null): SAH trees pad every
 // inner box by extent * 2^-19 so the FMA slab test (box_next) stays conservative.
@@ -286,6 +317,13 @@ struct rtw_ctx {
     std::vector<rtw_dev_quad> quads_host;
     std::vector<rtw_dev_sphere> spheres_host;
     std::vector<uint32_t> members_host, boundaries_host, mat_kind_host;
+    // vertex attributes (rtw_scene_set_vertex_attrs): the registered entries as given back by
+    // rtw_scene_vertex_attrs_get (normals normalised), the dense records parallel to quads_host (host context:
+    // base.vattrs addresses them) and their device copy (GPU context; allocated at the first registration)
+    std::vector<uint32_t> vattr_quads;
+    std::vector<rtw_vertex_attr> vattr_set;
+    std::vector<rtw_dev_vattr> vattrs_rec;
+    rtw_dev_vattr* d_vattrs = nullptr;
     float box_pad = 0;             // absolute pad baked into the inner boxes (SAH trees), 0 = none
     float extent = 0;              // max |coordinate| over the scene's boxes
     // Concurrent callers (the reference's 8 RenderThreads call Camera.render at once, main.zig:314-326):

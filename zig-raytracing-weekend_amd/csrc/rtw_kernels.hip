@@ -411,6 +411,8 @@ int occupancy_v1(size_t lds_bytes) {
 }
 
 uint32_t pick_feat(uint32_t f) {
+    // vertex attributes registered (rtw_feat_of): their two instantiations, on top of every feature and the trees
+    if (f & RTW_F_ATTR) return RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR | (f & RTW_F_PDF);
     // lights registered (rtw_feat_of): the mixture-density instantiations, on top of every feature
     if (f & RTW_F_PDF) return (f & RTW_F_TREE) ? (RTW_F_ALL | RTW_F_TREE | RTW_F_PDF) : (RTW_F_ALL | RTW_F_PDF);
     if ((f & ~RTW_F_CHECKER) == 0) return f ? RTW_F_CHECKER : 0u;
@@ -436,6 +438,10 @@ void rtw_launch_render(const rtw_launch& L, void* stream, int variant, int grid)
         dim3 block(256);
         dim3 g((L.W + 31) / 32, (L.n_rows + 7) / 8);
         switch (pick_feat(rtw_feat_of(L) | RTW_F_ALL)) {
+        case RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR: hipLaunchKernelGGL(render_pixels_v0<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR>, g, block, 0, st, L); break;
+        case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR:
+            hipLaunchKernelGGL(render_pixels_v0<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>, g, block, 0, st, L);
+            break;
         case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF:
             hipLaunchKernelGGL(render_pixels_v0<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF>, g, block, 0, st, L);
             break;
@@ -448,6 +454,13 @@ void rtw_launch_render(const rtw_launch& L, void* stream, int variant, int grid)
     const bool lds = L.n_nodes <= RTW_MEGA_LDS_NODES_MAX && L.use_lds;
     const int w = (int)L.waves;
     switch (pick_feat(rtw_feat_of(L))) {
+    case RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR:
+        lds ? launch_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR, true>(L, st, grid, w) : launch_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR, false>(L, st, grid, w);
+        break;
+    case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR:
+        lds ? launch_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR, true>(L, st, grid, w)
+            : launch_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR, false>(L, st, grid, w);
+        break;
     case RTW_F_ALL | RTW_F_PDF:
         lds ? launch_waves<RTW_F_ALL | RTW_F_PDF, true>(L, st, grid, w)
             : launch_waves<RTW_F_ALL | RTW_F_PDF, false>(L, st, grid, w);
@@ -481,6 +494,13 @@ int rtw_persistent_grid(uint32_t feat, uint32_t n_nodes, int waves, bool use_lds
     const size_t bytes = (size_t)n_nodes * 32;
     int b;
     switch (pick_feat(feat)) {
+    case RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR:
+        b = lds ? occ_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR, true>(bytes, waves) : occ_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR, false>(bytes, waves);
+        break;
+    case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR:
+        b = lds ? occ_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR, true>(bytes, waves)
+                : occ_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR, false>(bytes, waves);
+        break;
     case RTW_F_ALL | RTW_F_PDF:
         b = lds ? occ_waves<RTW_F_ALL | RTW_F_PDF, true>(bytes, waves) : occ_waves<RTW_F_ALL | RTW_F_PDF, false>(bytes, waves);
         break;
@@ -506,7 +526,13 @@ void rtw_launch_debug_rng(uint64_t seed, uint32_t pixel, uint32_t sample, uint32
 }
 
 void rtw_launch_debug_sample(const rtw_launch& L, uint32_t pixel, uint32_t sample, float* d_out, void* stream) {
-    if (L.n_lights && (L.feat & RTW_F_TREE))
+    if (L.vattrs && L.n_lights)
+        hipLaunchKernelGGL(debug_sample_kernel<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                           L, pixel, sample, d_out);
+    else if (L.vattrs)
+        hipLaunchKernelGGL(debug_sample_kernel<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR>, dim3(1), dim3(64), 0, (hipStream_t)stream, L,
+                           pixel, sample, d_out);
+    else if (L.n_lights && (L.feat & RTW_F_TREE))
         hipLaunchKernelGGL(debug_sample_kernel<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF>, dim3(1), dim3(64), 0, (hipStream_t)stream, L,
                            pixel, sample, d_out);
     else if (L.n_lights)

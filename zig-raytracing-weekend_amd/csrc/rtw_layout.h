@@ -80,6 +80,17 @@ struct rtw_dev_light {
 };
 static_assert(sizeof(rtw_dev_light) == 32, "light record must be 32 bytes");
 
+// 64 B: the per-vertex attributes of triangle quads[i] (rtw_scene_set_vertex_attrs), an array parallel to `quads`:
+// the fields of rtw_vertex_attr in its order -- four 16-B loads, taken only under `flags` (RTW_ATTR_*; 0: the quad
+// has none -- every parallelogram).  Corners in the order q, q + u, q + v; the normals are unit vectors (normalised
+// at registration), 0 without RTW_ATTR_NORMALS, as the uvs are without RTW_ATTR_UVS.
+struct alignas(16) rtw_dev_vattr {
+    float normal[3][3];
+    float uv[3][2];
+    uint32_t flags;
+};
+static_assert(sizeof(rtw_dev_vattr) == 64, "vertex attribute record must be 64 bytes");
+
 // 96 B: members[first .. first+count) (RTW_REF), xf[k] = {bits(kind), a, b, c}:
 // translate (a, b, c) = offset; rotate_y a = sin, b = cos.  xf[0] innermost.
 // tree: 0 = the members are tested one after another (list_t); else 1 + the index in rtw_launch.inodes of the

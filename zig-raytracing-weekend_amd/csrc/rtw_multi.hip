@@ -252,6 +252,15 @@ int rtw_multi_create(rtw_ctx* const* ctxs, uint32_t n, rtw_multi** out) {
                 return mfail(RTW_E_INVALID, "the contexts' light lists differ (rtw_scene_set_lights on each of them)");
             }
         }
+        // ... and the same vertex attributes
+        if (ctxs[0]->vattr_quads != ctxs[k]->vattr_quads ||
+            ctxs[0]->vattr_set.size() != ctxs[k]->vattr_set.size() ||
+            (!ctxs[0]->vattr_set.empty() &&
+             std::memcmp(ctxs[0]->vattr_set.data(), ctxs[k]->vattr_set.data(),
+                         ctxs[0]->vattr_set.size() * sizeof(rtw_vertex_attr)) != 0)) {
+            delete m;
+            return mfail(RTW_E_INVALID, "the contexts' vertex attributes differ (rtw_scene_set_vertex_attrs on each of them)");
+        }
         m->ctx.push_back(ctxs[k]);
         m->dev.push_back(ctxs[k]->device);
     }

@@ -2245,6 +2245,9 @@ void wf_run(const rtw_launch& L, const rtw_wf& W0, hipStream_t st, int n_cu, rtw
 #define RTW_F_TEXTURED (RTW_F_CHECKER | RTW_F_IMAGE | RTW_F_NOISE)
 #define RTW_F_MEDIA (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_LIGHT | RTW_F_CHECKER)
 uint32_t wf_pick_feat(uint32_t f) {
+    // vertex attributes registered (rtw_feat_of): their two instantiations, on top of every feature and the
+    // instance trees (a scene without a tree runs them too: inst_hit_t falls back to the member loop)
+    if (f & RTW_F_ATTR) return RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR | (f & RTW_F_PDF);
     // lights registered (rtw_feat_of): the mixture-density instantiations, on top of every feature
     if (f & RTW_F_PDF) return (f & RTW_F_TREE) ? (RTW_F_ALL | RTW_F_TREE | RTW_F_PDF) : (RTW_F_ALL | RTW_F_PDF);
     if (f & RTW_F_TREE) return RTW_F_ALL | RTW_F_TREE;  // instance trees (inst_tree_t): their own instantiation
@@ -2257,7 +2260,23 @@ uint32_t wf_pick_feat(uint32_t f) {
 
 }  // namespace
 
-#if defined(RTW_WF_LIGHTS_TU)
+#if defined(RTW_WF_ATTRS_TU)
+// contexts with registered vertex attributes (rtw_feat_of: RTW_F_ATTR) run from rtw_wavefront_attrs.hip
+void rtw_wf_run_attrs(const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, rtw_timer* T, bool pdf) {
+    if (pdf) wf_run<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>(L, W, st, n_cu, T);
+    else wf_run<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR>(L, W, st, n_cu, T);
+}
+
+// (waves of the 256-thread shade grids, as rtw_wavefront_max_waves counts the other classes')
+uint32_t rtw_wf_attrs_max_waves(int n_cu) {
+    uint32_t m = 0;
+    auto mx = [&m](uint32_t a, uint32_t b) { m = std::max({m, a, b}); };
+    mx(wf_grids<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR>(n_cu).shade, wf_grids<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR>(n_cu).shade0);
+    mx(wf_grids<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>(n_cu).shade,
+       wf_grids<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>(n_cu).shade0);
+    return 4 * m;
+}
+#elif defined(RTW_WF_LIGHTS_TU)
 // contexts with registered lights (rtw_feat_of: RTW_F_PDF) run from rtw_wavefront_lights.hip
 void rtw_wf_run_lights(const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, rtw_timer* T, bool tree) {
     if (tree) wf_run<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF>(L, W, st, n_cu, T);
@@ -2281,10 +2300,15 @@ uint32_t rtw_wf_spheres_max_waves(int n_cu);
 // contexts with registered lights (the RTW_F_PDF instantiations) from rtw_wavefront_lights.hip
 void rtw_wf_run_lights(const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, rtw_timer* T, bool tree);
 uint32_t rtw_wf_lights_max_waves(int n_cu);
+// contexts with registered vertex attributes (the RTW_F_ATTR instantiations) from rtw_wavefront_attrs.hip
+void rtw_wf_run_attrs(const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, rtw_timer* T, bool pdf);
+uint32_t rtw_wf_attrs_max_waves(int n_cu);
 
 void rtw_wavefront_batch(const rtw_launch& L, const rtw_wf& W, void* stream, int n_cu, rtw_timer* T) {
     hipStream_t st = (hipStream_t)stream;
     switch (wf_pick_feat(rtw_feat_of(L))) {
+    case RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR: rtw_wf_run_attrs(L, W, st, n_cu, T, false); break;
+    case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR: rtw_wf_run_attrs(L, W, st, n_cu, T, true); break;
     case RTW_F_ALL | RTW_F_PDF: rtw_wf_run_lights(L, W, st, n_cu, T, false); break;
     case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF: rtw_wf_run_lights(L, W, st, n_cu, T, true); break;
     case 0u: rtw_wf_run_spheres(L, W, st, n_cu, T, 0u); break;
@@ -2307,7 +2331,7 @@ uint32_t rtw_wavefront_max_waves(int n_cu) {
     mx(wf_grids<RTW_F_MEDIA>(n_cu).shade, wf_grids<RTW_F_MEDIA>(n_cu).shade0);
     mx(wf_grids<RTW_F_ALL>(n_cu).shade, wf_grids<RTW_F_ALL>(n_cu).shade0);
     mx(wf_grids<RTW_F_ALL | RTW_F_TREE>(n_cu).shade, wf_grids<RTW_F_ALL | RTW_F_TREE>(n_cu).shade0);
-    return std::max({4 * m, rtw_wf_spheres_max_waves(n_cu), rtw_wf_lights_max_waves(n_cu)});
+    return std::max({4 * m, rtw_wf_spheres_max_waves(n_cu), rtw_wf_lights_max_waves(n_cu), rtw_wf_attrs_max_waves(n_cu)});
 }
 #else
 void rtw_wf_run_spheres(const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, rtw_timer* T, uint32_t feat) {

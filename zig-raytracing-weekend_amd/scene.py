@@ -207,12 +207,16 @@ class Sphere:
 class Quad:
     """Quad.init (objects.zig:201-210); the library derives normal, d, w and the box.
 
-    shape: RTW_QUAD_PARALLELOGRAM, or RTW_QUAD_TRIANGLE -- the triangle q, q + u, q + v (``Triangle.init``)."""
+    shape: RTW_QUAD_PARALLELOGRAM, or RTW_QUAD_TRIANGLE -- the triangle q, q + u, q + v (``Triangle.init``).
+    normals / uvs (triangles only): per-corner shading normals (3, 3) and texture coordinates (3, 2), corners in
+    the order q, q + u, q + v; None = the geometric normal / (alpha, beta)."""
     q: np.ndarray
     u: np.ndarray
     v: np.ndarray
     mat: Material
     shape: int = _abi.RTW_QUAD_PARALLELOGRAM
+    normals: Optional[np.ndarray] = None
+    uvs: Optional[np.ndarray] = None
 
     @staticmethod
     def init(q, u, v, mat: Material) -> "Quad":
@@ -222,12 +226,19 @@ class Quad:
 class Triangle:
     """The book's first "additional 2D primitive": a Quad record with another interior test (alpha + beta <= 1,
     inclusive like the quad's edges).  Plane, normal (cross(b - a, c - a)), front face and (u, v) = (alpha, beta)
-    are the quad's; the box is that of the three vertices."""
+    are the quad's; the box is that of the three vertices.
+
+    normals (3, 3) / uvs (3, 2): per-vertex shading normals (any length but zero) and texture coordinates of a, b,
+    c, interpolated over the face (smooth shading; ``World`` registers them, rtw_scene_set_vertex_attrs)."""
 
     @staticmethod
-    def init(a, b, c, mat: Material) -> Quad:
+    def init(a, b, c, mat: Material, normals=None, uvs=None) -> Quad:
         a = _v3(a)
-        return Quad(a, _v3(b) - a, _v3(c) - a, mat, _abi.RTW_QUAD_TRIANGLE)
+        if normals is not None:
+            normals = np.array(normals, dtype=np.float32).reshape(3, 3)
+        if uvs is not None:
+            uvs = np.array(uvs, dtype=np.float32).reshape(3, 2)
+        return Quad(a, _v3(b) - a, _v3(c) - a, mat, _abi.RTW_QUAD_TRIANGLE, normals, uvs)
 
 
 def quad_triangles(quad: Quad) -> List[Quad]:
@@ -260,30 +271,68 @@ class HittableList:
 class Mesh(HittableList):
     """A triangle mesh: a HittableList of ``Triangle``s over shared vertices -- bare or under Translate / RotateY
     it is an instance (more than 127 triangles: with a private BVH, as any list; ``bvh`` as HittableList's), and
-    as such a ConstantMedium boundary.  Flat shading: no per-vertex normals or texture coordinates."""
+    as such a ConstantMedium boundary.
+
+    normals (n, 3) / uvs (n, 2): per-vertex shading normals and texture coordinates, interpolated over each face;
+    face_normals / face_uvs (m, 3): the corners' indices into them, where they differ from ``faces`` (an OBJ file's
+    ``i/j/k``); a face with a negative index there gets no attribute of that kind."""
     vertices: np.ndarray = None   # (n, 3) f32
     faces: np.ndarray = None      # (m, 3) vertex indices
 
     @staticmethod
-    def init(vertices, faces, mat: Material, bvh: Optional[bool] = None) -> "Mesh":
+    def init(vertices, faces, mat: Material, bvh: Optional[bool] = None, normals=None, uvs=None, face_normals=None,
+             face_uvs=None) -> "Mesh":
         v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
         f = np.ascontiguousarray(faces, dtype=np.int64).reshape(-1, 3)
         if len(f) and (f.min() < 0 or f.max() >= len(v)):
             raise ValueError("face index out of range")
-        return Mesh([Triangle.init(v[i], v[j], v[k], mat) for i, j, k in f], bvh, v, f)
+
+        def corner_values(values, index, width, what):
+            if values is None:
+                if index is not None:
+                    raise ValueError(f"face_{what} without {what}")
+                return None, None
+            a = np.ascontiguousarray(values, dtype=np.float32).reshape(-1, width)
+            ix = f if index is None else np.ascontiguousarray(index, dtype=np.int64).reshape(-1, 3)
+            if ix.shape != f.shape:
+                raise ValueError(f"face_{what}: one index triple per face")
+            if len(ix) and ix.max() >= len(a):
+                raise ValueError(f"{what} index out of range")
+            return a, ix
+
+        vn, fn = corner_values(normals, face_normals, 3, "normals")
+        vt, ft = corner_values(uvs, face_uvs, 2, "uvs")
+        tris = []
+        for m, (i, j, k) in enumerate(f):
+            tn = vn[fn[m]] if vn is not None and fn[m].min() >= 0 else None
+            tt = vt[ft[m]] if vt is not None and ft[m].min() >= 0 else None
+            tris.append(Triangle.init(v[i], v[j], v[k], mat, tn, tt))
+        return Mesh(tris, bvh, v, f)
 
 
-def load_obj(path_or_text: str, mat: Material, bvh: Optional[bool] = None) -> Mesh:
-    """A Wavefront OBJ file (or its text, if the argument has a line break) as a Mesh: ``v`` and ``f`` lines only
-    -- face corners ``i``, ``i/j``, ``i/j/k`` or ``i//k`` (the vertex index is used), 1-based or negative
-    (relative to the vertices read so far), polygons as fans about their first corner.  Everything else is
-    ignored; an index out of range raises ValueError."""
+def load_obj(path_or_text: str, mat: Material, bvh: Optional[bool] = None, attributes: bool = False) -> Mesh:
+    """A Wavefront OBJ file (or its text, if the argument has a line break) as a Mesh: ``v`` and ``f`` lines
+    -- face corners ``i``, ``i/j``, ``i/j/k`` or ``i//k``, 1-based or negative (relative to the vertices read so
+    far), polygons as fans about their first corner.  Everything else is ignored; an index out of range raises
+    ValueError.
+
+    attributes: False = the vertex index of a corner alone is used (flat shading, ``vn`` / ``vt`` lines ignored);
+    True = ``vn`` and ``vt`` lines are read too and a face whose corners all carry a ``k`` (``j``) gets per-vertex
+    normals (uvs); a ``vn`` / ``vt`` index out of range raises ValueError naming the line."""
     if "\n" in path_or_text:
         text = path_or_text
     else:
         with open(path_or_text) as fh:
             text = fh.read()
-    verts, faces = [], []
+    verts, faces, vns, vts, fns, fts = [], [], [], [], [], []
+
+    def index(ln, text, have, what):
+        i = int(text)
+        k = i - 1 if i > 0 else len(have) + i
+        if i == 0 or not 0 <= k < len(have):
+            raise ValueError(f"line {ln}: {what} index {i} out of range ({len(have)} so far)")
+        return k
+
     for ln, line in enumerate(text.splitlines(), 1):
         tok = line.split("#", 1)[0].split()
         if not tok:
@@ -292,18 +341,40 @@ def load_obj(path_or_text: str, mat: Material, bvh: Optional[bool] = None) -> Me
             if len(tok) < 4:
                 raise ValueError(f"line {ln}: a vertex needs three coordinates")
             verts.append([float(x) for x in tok[1:4]])
+        elif tok[0] == "vn" and attributes:
+            if len(tok) < 4:
+                raise ValueError(f"line {ln}: a normal needs three coordinates")
+            vns.append([float(x) for x in tok[1:4]])
+        elif tok[0] == "vt" and attributes:
+            if len(tok) < 3:
+                raise ValueError(f"line {ln}: a texture coordinate needs two values")
+            vts.append([float(x) for x in tok[1:3]])
         elif tok[0] == "f":
-            corners = []
+            corners, cn, ct = [], [], []
             for c in tok[1:]:
-                i = int(c.split("/", 1)[0])
+                part = c.split("/")
+                i = int(part[0])
                 k = i - 1 if i > 0 else len(verts) + i
                 if i == 0 or not 0 <= k < len(verts):
                     raise ValueError(f"line {ln}: vertex index {i} out of range ({len(verts)} vertices so far)")
                 corners.append(k)
+                if attributes:   # -1: the corner has none
+                    ct.append(index(ln, part[1], vts, "vt") if len(part) > 1 and part[1] else -1)
+                    cn.append(index(ln, part[2], vns, "vn") if len(part) > 2 and part[2] else -1)
             if len(corners) < 3:
                 raise ValueError(f"line {ln}: a face needs three corners")
-            faces += [(corners[0], corners[j], corners[j + 1]) for j in range(1, len(corners) - 1)]
-    return Mesh.init(np.array(verts, np.float32).reshape(-1, 3), np.array(faces, np.int64).reshape(-1, 3), mat, bvh)
+            fan = range(1, len(corners) - 1)
+            faces += [(corners[0], corners[j], corners[j + 1]) for j in fan]
+            if attributes:
+                fns += [(cn[0], cn[j], cn[j + 1]) for j in fan]
+                fts += [(ct[0], ct[j], ct[j + 1]) for j in fan]
+    v, f = np.array(verts, np.float32).reshape(-1, 3), np.array(faces, np.int64).reshape(-1, 3)
+    if not attributes:
+        return Mesh.init(v, f, mat, bvh)
+    return Mesh.init(v, f, mat, bvh, normals=np.array(vns, np.float32).reshape(-1, 3) if vns else None,
+                     uvs=np.array(vts, np.float32).reshape(-1, 2) if vts else None,
+                     face_normals=np.array(fns, np.int64).reshape(-1, 3) if vns else None,
+                     face_uvs=np.array(fts, np.int64).reshape(-1, 3) if vts else None)
 
 
 @dataclass(eq=False)
@@ -380,6 +451,9 @@ class SceneArrays:
     media: np.ndarray = field(default_factory=lambda: np.zeros(0, _abi.MEDIUM_DT))
     objects: Optional[np.ndarray] = None   # world_objects order; None = every sphere in order
     lights: Optional[np.ndarray] = None    # rtw_object records World registers (rtw_scene_set_lights); None = none
+    # (quad indices u4, VERTEX_ATTR_DT records) of the triangles with per-vertex normals / uvs, which World
+    # registers (rtw_scene_set_vertex_attrs); None = none
+    vertex_attrs: Optional[tuple] = None
 
     def desc(self):
         """Build an RtwSceneDesc (keeps the ctypes image array alive on self)."""
@@ -462,6 +536,7 @@ def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None
         return len(mats) - 1
 
     where = {}   # id(primitive) -> its (kind, index) record, for `lights`
+    attr_quads, attr_recs = [], []   # the triangles with normals / uvs: quad index, VERTEX_ATTR_DT record
 
     def prim(o) -> tuple:
         where[id(o)] = ref = new_prim(o)
@@ -484,6 +559,16 @@ def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None
             _abi.quad_shape(rec)[...] = o.shape
             rec["material"] = mat_index(o.mat)
             quads.append(rec)
+            if o.normals is not None or o.uvs is not None:
+                if o.shape != _abi.RTW_QUAD_TRIANGLE:
+                    raise ValueError("normals / uvs on a parallelogram (only triangles take vertex attributes)")
+                a = np.zeros((), _abi.VERTEX_ATTR_DT)
+                if o.normals is not None:
+                    a["normal"], a["flags"] = o.normals, a["flags"] | _abi.RTW_ATTR_NORMALS
+                if o.uvs is not None:
+                    a["uv"], a["flags"] = o.uvs, a["flags"] | _abi.RTW_ATTR_UVS
+                attr_quads.append(len(quads) - 1)
+                attr_recs.append(a)
             return (_abi.RTW_OBJ_QUAD, len(quads) - 1)
         raise TypeError(f"not a primitive: {type(o).__name__}")
 
@@ -558,7 +643,9 @@ def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None
                        quads=arr(quads, _abi.QUAD_DT), members=arr(members, _abi.OBJECT_DT),
                        instances=arr(instances, _abi.INSTANCE_DT), media=arr(media, _abi.MEDIUM_DT),
                        objects=None if only_spheres else arr(objs, _abi.OBJECT_DT),
-                       lights=None if light_refs is None else arr(light_refs, _abi.OBJECT_DT))
+                       lights=None if light_refs is None else arr(light_refs, _abi.OBJECT_DT),
+                       vertex_attrs=(np.array(attr_quads, np.uint32), arr(attr_recs, _abi.VERTEX_ATTR_DT))
+                       if attr_quads else None)
 
 
 def flatten_bvh(arrays: SceneArrays) -> np.ndarray:
@@ -592,12 +679,14 @@ class World:
         else:
             _abi.check(L.rtw_scene_create(C.byref(self._desc), device, C.byref(h)), "rtw_scene_create")
         self.handle = h
-        if arrays.lights is not None and len(arrays.lights):
-            try:
+        try:
+            if arrays.lights is not None and len(arrays.lights):
                 self.set_lights(arrays.lights)
-            except Exception:
-                self.close()
-                raise
+            if arrays.vertex_attrs is not None and len(arrays.vertex_attrs[0]):
+                self.set_vertex_attrs(*arrays.vertex_attrs)
+        except Exception:
+            self.close()
+            raise
 
     def set_lights(self, lights) -> None:
         """rtw_scene_set_lights: the quads and spheres diffuse scatter samples towards -- an OBJECT_DT array,
@@ -617,6 +706,28 @@ class World:
         if n.value:
             _abi.check(f(self.handle, out.ctypes.data, n.value, C.byref(n)), "rtw_scene_lights_get")
         return out
+
+    def set_vertex_attrs(self, quads, attrs=None) -> None:
+        """rtw_scene_set_vertex_attrs: per-vertex normals / uvs of triangles -- quad indices and as many
+        VERTEX_ATTR_DT records, or None / empty to clear (the world then renders exactly as one never given any).
+        Replaces the registered set.  Must not race a render on this world."""
+        q = np.zeros(0, np.uint32) if quads is None else np.ascontiguousarray(quads, dtype=np.uint32).reshape(-1)
+        a = np.zeros(0, _abi.VERTEX_ATTR_DT) if attrs is None else np.ascontiguousarray(attrs, dtype=_abi.VERTEX_ATTR_DT).reshape(-1)
+        if len(q) != len(a):
+            raise ValueError("set_vertex_attrs: one record per quad index")
+        _abi.check(_abi.lib().rtw_scene_set_vertex_attrs(self.handle, _abi.ptr(q), _abi.ptr(a), len(q)),
+                   "rtw_scene_set_vertex_attrs")
+
+    def vertex_attrs(self) -> tuple:
+        """The registered vertex attributes (rtw_scene_vertex_attrs_get): (quad indices, VERTEX_ATTR_DT records),
+        the normals as stored (unit vectors)."""
+        n = C.c_uint32()
+        f = _abi.lib().rtw_scene_vertex_attrs_get
+        _abi.check(f(self.handle, None, None, 0, C.byref(n)), "rtw_scene_vertex_attrs_get")
+        q, a = np.zeros(n.value, np.uint32), np.zeros(n.value, _abi.VERTEX_ATTR_DT)
+        if n.value:
+            _abi.check(f(self.handle, q.ctypes.data, a.ctypes.data, n.value, C.byref(n)), "rtw_scene_vertex_attrs_get")
+        return q, a
 
     def close(self):
         if getattr(self, "handle", None) and self.handle.value:

@@ -216,10 +216,16 @@ def cornell_smoke() -> list:
     return objs
 
 
-def icosphere(level: int, centre, radius, mat, bvh: Optional[bool] = None) -> Mesh:
+def icosphere(level: int, centre, radius, mat, bvh: Optional[bool] = None, smooth: bool = False,
+              uv: bool = False) -> Mesh:
     """A sphere of 20 * 4^level triangles (generated, not loaded): the icosahedron, every triangle split in four
     `level` times, the new vertices pushed out to the sphere.  Closed, every edge shared by two triangles, normals
-    (cross(b - a, c - a)) outward.  Vertices are computed in float64 and rounded once."""
+    (cross(b - a, c - a)) outward.  Vertices are computed in float64 and rounded once.
+
+    smooth: per-vertex normals, the vertex directions (the shading normal of a point of a face is then the
+    sphere's at the point's direction).  uv: per-corner texture coordinates, the Sphere's own (u, v) of the vertex
+    direction (getSphereUV); a face across the u = 1 | 0 seam continues past 1 (an image texture clamps there), and
+    a pole vertex, whose u is arbitrary, takes the mean u of its face's other corners."""
     t = (1.0 + 5.0 ** 0.5) / 2.0
     verts = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t),
              (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
@@ -243,16 +249,33 @@ def icosphere(level: int, centre, radius, mat, bvh: Optional[bool] = None) -> Me
             ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
             split += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
         faces = split
-    v = np.asarray(centre, np.float64).reshape(3) + float(radius) * np.array(verts)
-    return Mesh.init(v.astype(np.float32), np.array(faces, np.int64), mat, bvh)
+    dirs = np.array(verts)
+    faces = np.array(faces, np.int64)
+    v = np.asarray(centre, np.float64).reshape(3) + float(radius) * dirs
+    uvs = face_uvs = None
+    if uv:
+        u = (np.arctan2(-dirs[:, 2], dirs[:, 0]) + np.pi) / (2 * np.pi)
+        uvs = np.stack([u, np.arccos(np.clip(-dirs[:, 1], -1, 1)) / np.pi], 1)[faces]   # (m, 3, 2) per corner
+        pole = np.abs(dirs[:, 1])[faces] > 1 - 1e-12
+        for tri, pl in zip(uvs, pole):
+            rest = tri[~pl, 0]
+            if rest.max() - rest.min() > 0.5:
+                rest[rest < 0.5] += 1.0
+            tri[~pl, 0] = rest
+            tri[pl, 0] = rest.mean()
+        uvs = uvs.reshape(-1, 2)
+        face_uvs = np.arange(len(uvs)).reshape(-1, 3)
+    return Mesh.init(v.astype(np.float32), faces, mat, bvh, normals=dirs if smooth else None, uvs=uvs,
+                     face_uvs=face_uvs)
 
 
-def cornell_mesh(level: int = 2, analytic: bool = False) -> list:
+def cornell_mesh(level: int = 2, analytic: bool = False, smooth: bool = False) -> list:
     """The Cornell box (camera: camera.cornell_camera) with triangles in every place a scene can hold them: the
     ceiling light as two emissive triangles, the tall box replaced by an icosphere of 20 * 4^level triangles under
     RotateY + Translate (level 2: 320, an instance with a private BVH), the short box by its 12 triangles (an
     instance tested as a list), and one free-standing top-level triangle.  analytic: the icosphere's place taken by
-    the Sphere it approximates (the price of the mesh, for measurements)."""
+    the Sphere it approximates (the price of the mesh, for measurements).  smooth: the icosphere with per-vertex
+    normals (icosphere(smooth=True))."""
     walls, white = _cornell_walls([343, 554, 332], [-130, 0, 0], [0, 0, -105], [15, 15, 15])
     objs = []
     for q in walls:
@@ -261,7 +284,7 @@ def cornell_mesh(level: int = 2, analytic: bool = False) -> list:
         ball = HittableList.init()
         ball.add(Sphere.init([82.5, 100, 82.5], 90, white))
     else:
-        ball = icosphere(level, [82.5, 100, 82.5], 90, white)
+        ball = icosphere(level, [82.5, 100, 82.5], 90, white, smooth=smooth)
     objs.append(Translate.init(RotateY.init(ball, 15), [265, 0, 295]))
     box = HittableList.init()
     for side in createBox([0, 0, 0], [165, 165, 165], white).objects:
