@@ -24,8 +24,6 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <map>
-#include <mutex>
 
 // Waves-per-SIMD targets of the 256-thread kernels (1 = no target: the registers the code needs;
 // MI355X_MICROARCH.md: <= 96 VGPRs -> 5 waves, <= 80 -> 6, <= 72 -> 7), same-box A/Bs of round 6
@@ -44,18 +42,6 @@
 #ifndef RTW_WPE_TAIL_W5
 #define RTW_WPE_TAIL_W5 6
 #endif
-// The media scenes' LDS tail parks the path state it does not need during the walk in LDS (wf_tail_body PARK):
-// Cornell smoke's tail 112 -> 80 B of scratch, -6.5 % tail time (+3 %); Cornell's (no media) loses 0.7 % with it
-// (same box, profiles/r6_waves/j/)
-#ifndef RTW_TAIL_PARK
-#define RTW_TAIL_PARK 1
-#endif
-// the cooperative rejection loop in the textured fused step too: once round 6 freed its registers (the IT0
-// split, the hit record after the loop) C5 +0.6 % (two rounds, profiles/r6_waves/l/; round 4: -2.3 % at the cap)
-#ifndef RTW_COOP_TEXTURED
-#define RTW_COOP_TEXTURED 1
-#endif
-
 #ifndef RTW_WPE_TAIL_LDS  // object classes with media / textures / motion; the plain one RTW_WPE_TAIL_LDS_OBJ
 #define RTW_WPE_TAIL_LDS 5
 #endif
@@ -1419,8 +1405,11 @@ __device__ __forceinline__ rtw_launch stage_shade(const rtw_launch& L, float4* l
 template <uint32_t FEAT, int CNT = 2>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wf_tail_lds_wpe<FEAT>()))) void wf_tail_lds(rtw_launch L, rtw_wf W, uint32_t it) {
     extern __shared__ float4 wf_tail_nodes[];
-    // (the media class only: the all-features class of simple_light carries the medium bit too, and lost with it)
-    constexpr bool kPark = RTW_TAIL_PARK && (FEAT & RTW_F_MEDIUM) != 0 &&
+    // The media scenes' LDS tail parks the path state it does not need during the walk in LDS (wf_tail_body PARK):
+    // Cornell smoke's tail 112 -> 80 B of scratch, -6.5 % tail time (+3 %); Cornell's (no media) loses 0.7 % with it
+    // (same box, profiles/r6_waves/j/).  The media class only: the all-features class of simple_light carries the
+    // medium bit too, and lost with it.
+    constexpr bool kPark = (FEAT & RTW_F_MEDIUM) != 0 &&
                            (FEAT & (RTW_F_IMAGE | RTW_F_NOISE | RTW_F_MOVING)) == 0;
     __shared__ float4 park_lds[kPark ? 512 : 1];
     float4* park = park_lds;
@@ -1506,13 +1495,11 @@ __device__ __forceinline__ int wf_walk(const rtw_launch& L, const void* lds, con
 // previous iteration, or by the host for it = 0) and zeroes len[(it+2)%3],
 // iteration it-1's input, for the next iteration.
 // the fused step loads a path's throughput / id / RNG state after its walk (late_rest in wf_step_body): every
-// scene class whose walk does not key media draws on the RNG state (object scenes: RTW_OBJ_LATE, an A/B switch)
-#ifndef RTW_OBJ_LATE
-#define RTW_OBJ_LATE 0
-#endif
+// sphere-scene class (their walks do not key media draws on the RNG state; object scenes measured +-0 with it on
+// Cornell and simple_light, profiles/r6_waves/g/, and keep the early load)
 template <uint32_t FEAT>
 constexpr bool wf_late_rest() {
-    return (FEAT & RTW_F_MEDIUM) == 0 && ((FEAT & RTW_F_GEOM) == 0 || RTW_OBJ_LATE);
+    return (FEAT & (RTW_F_MEDIUM | RTW_F_GEOM)) == 0;
 }
 
 // IT0: 1 = the launch of iteration 0 (camera rays), 0 = a launch of iteration >= 1, 2 = either (runtime `it`)
@@ -1621,9 +1608,10 @@ __device__ __forceinline__ void wf_step_body(const rtw_launch& L, const rtw_wf& 
                 }
             }
             float uv3[3] = {0.0f, 0.0f, 0.0f};
-            // the wave-cooperative loop (same candidates, same RNG states as seq_reject<3>): C2 +1.4 %, C5 +0.6 %
-            if constexpr ((FEAT & (RTW_F_IMAGE | RTW_F_NOISE)) == 0 || RTW_COOP_TEXTURED) wf_reject3(need_uv, rng, uv3);
-            else if (need_uv) seq_reject<3>(rng, uv3);
+            // the wave-cooperative loop (same candidates, same RNG states as seq_reject<3>): C2 +1.4 %; in the
+            // textured step too once round 6 freed its registers (the IT0 split, the hit record after the loop):
+            // C5 +0.6 % (two rounds, profiles/r6_waves/l/; round 4: -2.3 % at the cap)
+            wf_reject3(need_uv, rng, uv3);
             if (hitp) hp = hit_prep<FEAT>(L.nodes, L, r, hhit, ht);
             if (hitp) {
                 const f3 ruv = need_uv ? unit_vector(mk(uv3[0], uv3[1], uv3[2])) : mk(0, 0, 0);
@@ -1713,10 +1701,7 @@ __global__ __launch_bounds__(1024) void wf_step_clds(rtw_launch L, rtw_wf W, uin
 // diag/walk_variants.patch -- and were removed in round 6.)
 // Iteration 0 (camera rays: wf_camera, the tile lists) and the later iterations (late_rest) of the fused steps in
 // separate instantiations, so that neither pays for the other's registers: C2's step scratch 64 -> 44 / 28 B,
-// C2 +1.8 % (same box, profiles/r6_waves/i/; C5, Cornell, smoke +-0.6 %).  0 = one instantiation (A/B).
-#ifndef RTW_STEP_IT0
-#define RTW_STEP_IT0 1
-#endif
+// C2 +1.8 % (same box, profiles/r6_waves/i/; C5, Cornell, smoke +-0.6 %).
 template <uint32_t FEAT, uint32_t T, int CNT = 2, int IT0 = 2>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(2 * T / 256)))
 void wf_step_clds2(rtw_launch L, rtw_wf W, uint32_t it) {
@@ -1822,556 +1807,6 @@ __global__ __launch_bounds__(256) void wf_reduce(rtw_launch L, rtw_wf W) {
     flush_counters(L, cnt, samples);
 }
 
-// resident blocks of `kernel`, rounded down to whole stripes of waves
-template <typename K>
-uint32_t wf_grid(K kernel, int n_cu, size_t lds = 0, uint32_t threads = 256) {
-    int b = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kernel, (int)threads, lds) != hipSuccess || b < 1) b = 1;
-    uint32_t g = (uint32_t)(b * n_cu);
-    // whole sets of stripes: the grid's waves a multiple of RTW_WF_STRIPES (every stripe the same number of
-    // waves, WfIter), i.e. blocks a multiple of 256 / gcd(256, waves per block)
-    uint32_t wpb = threads / 64, gcd = RTW_WF_STRIPES;
-    for (uint32_t a = wpb; a;) {
-        const uint32_t t = gcd % a;
-        gcd = a;
-        a = t;
-    }
-    const uint32_t per = RTW_WF_STRIPES / gcd;
-    g -= g % per;
-    return g ? g : per;
-}
-
-// grid-cache key of a launch shape on a device of n_cu CUs (never 0: an empty cache misses).  Every cache is
-// per host thread and keyed by the CU count too: a grid larger than the device's would overflow the stripes
-// that rtw_wavefront_max_waves(n_cu) sized.
-inline uint64_t wf_key(int n_cu, uint64_t shape) { return ((uint64_t)(uint32_t)n_cu << 40) | (shape + 1u); }
-
-// the same, cached per host thread for one dynamic LDS size (c = {grid, key})
-template <typename K>
-uint32_t wf_grid_cached(K kernel, int n_cu, size_t lds, uint64_t (&c)[2]) {
-    if (c[1] != wf_key(n_cu, lds)) {
-        c[0] = wf_grid(kernel, n_cu, lds);
-        c[1] = wf_key(n_cu, lds);
-    }
-    return (uint32_t)c[0];
-}
-
-// the global tail launch of either form
-template <uint32_t FEAT>
-void wf_launch_tail(const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, size_t lds, uint64_t (&cache)[2],
-                    uint32_t it) {
-    if constexpr ((FEAT & ~RTW_F_CHECKER) == 0)
-        { if (L.counters) hipLaunchKernelGGL((wf_tail_w5<FEAT, 1>), dim3(wf_grid_cached(wf_tail_w5<FEAT, 0>, n_cu, lds, cache)), dim3(256),
-                                        lds, st, L, W, it); else hipLaunchKernelGGL((wf_tail_w5<FEAT, 0>), dim3(wf_grid_cached(wf_tail_w5<FEAT, 0>, n_cu, lds, cache)), dim3(256),
-                                        lds, st, L, W, it); }
-    else
-        hipLaunchKernelGGL(wf_tail<FEAT>, dim3(wf_grid_cached(wf_tail<FEAT>, n_cu, lds, cache)), dim3(256), lds, st, L,
-                           W, it);
-}
-
-// dynamic LDS of the kernels that walk through L1/L2: the two-wide walk's per-lane stacks
-template <uint32_t FEAT>
-size_t wf_w2_lds(const rtw_launch& L) {
-    if constexpr ((FEAT & (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_MOVING)) == 0) {
-        if (L.w2nodes && L.fast_box) return (size_t)256u * 4u * L.w2_stack;
-    }
-    return 0;
-}
-
-// The camera-ray candidate lists of a batch (static sphere scenes with the compact nodes): the
-// flat scan for small trees, the frustum walk for large ones.  Returns W with tl_count null when off.
-template <uint32_t FEAT>
-rtw_wf wf_lists(const rtw_launch& L, const rtw_wf& W, hipStream_t st) {
-    rtw_wf Wt = W;
-    if (!W.tl_count || !L.cnodes || (FEAT & (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_MOVING)) || L.max_depth == 0) {
-        Wt.tl_count = nullptr;
-        return Wt;
-    }
-    const uint32_t tiles = W.n_pix / 64u;
-    if (L.n_nodes <= 4096u)
-        hipLaunchKernelGGL(wf_tile_lists, dim3(tiles), dim3(64), 0, st, L, Wt);
-    else
-        hipLaunchKernelGGL(wf_tile_lists_walk, dim3((tiles + 63u) / 64u), dim3(64), 0, st, L, Wt);
-    return Wt;
-}
-
-// Coherent-queue settings of a launch whose grid has nw waves.  Iteration 0 deals runs of
-// up to 16 samples per tile, shorter when a wave would get fewer than 64 runs (a small batch: whole runs
-// would leave the waves' shares of work uneven); direction bucketing only when a wave's iteration 0 has at
-// least RTW_WF_SORT_MIN_CHUNKS chunks -- each open block ends its iteration partly dead, which only a large
-// share of survivors per wave amortises (simple_light, 137 chunks per wave: -10 % with bucketing).  Deal bit 128
-// (RTW_DEAL_SMALL_SORT) lifts that gate, so the tests run the bucketed queues of the large benched batches on small
-// images (tests/test_gpu_parity.py, test_gpu_objects.py).
-#define RTW_WF_SORT_MIN_CHUNKS 192u
-rtw_wf wf_coherence(const rtw_wf& W, uint32_t nw, uint32_t sort_iters) {
-    rtw_wf C = W;
-    const uint32_t per_wave = nw ? (W.n_paths >> 6) / nw : 0u;
-    uint32_t lg = 0;
-    while (lg < 4 && (per_wave >> (lg + 1)) >= 64u) lg++;
-    // the dynamic deal only where the waves have enough work to share: a small batch (simple_light, 137 chunks per
-    // wave) ran 6 % slower with it -- its tail's claims cost more than they balance (profiles/r5_deal/)
-    if (per_wave < RTW_WF_SORT_MIN_CHUNKS && !(C.deal_mode & 8u)) C.deal = nullptr;  // (bit 8: tests force it)
-    if (C.deal && (C.deal_mode & 1u)) lg = 4;  // dynamic deal: the waves balance themselves, runs keep 16 samples
-    C.run_log2 = lg;
-    C.sort_iters = (per_wave >= RTW_WF_SORT_MIN_CHUNKS || (C.deal_mode & 128u)) ? sort_iters : 0u;
-    return C;
-}
-
-template <uint32_t FEAT>
-struct WfGrids {
-    uint32_t shade = 0, shade0 = 0;  // shade0: iteration 0's instantiation (wf_camera)
-    WfGrids() = default;
-    explicit WfGrids(int n_cu)
-        : shade(wf_grid(wf_shade<FEAT>, n_cu)), shade0(wf_grid(wf_shade<FEAT, true>, n_cu)) {}
-};
-
-// largest LDS stage of the wavefront trace (bytes); larger trees read L1/L2
-#define RTW_WF_LDS_MAX (64u * 1024u)
-#define RTW_WF_CLDS_MAX (150u * 1024u)  // compact-node LDS stage (one 1024-thread block per CU)
-
-template <uint32_t FEAT, bool CAM>
-uint32_t wf_lds_grid(int n_cu, size_t lds) {
-    thread_local uint32_t cache[(RTW_WF_LDS_MAX + 16384) / 512 + 1] = {0};  // + geometry (L.geom_lds)
-    thread_local int cache_cu = 0;
-    if (cache_cu != n_cu) {
-        for (uint32_t& c : cache) c = 0;
-        cache_cu = n_cu;
-    }
-    uint32_t& g = cache[lds / 512];
-    if (!g) g = wf_grid(wf_trace<FEAT, true, CAM>, n_cu, lds);
-    return g;
-}
-
-// per CU count (a process may render on devices or partitions of different sizes), process-wide: the 8
-// Tasks of a render (main.zig:314-326) share one set instead of each thread querying the occupancy API again
-template <uint32_t FEAT>
-WfGrids<FEAT> wf_grids(int n_cu) {
-    static std::mutex mu;
-    static std::map<int, WfGrids<FEAT>> cache;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find(n_cu);
-    if (it == cache.end()) it = cache.emplace(n_cu, WfGrids<FEAT>(n_cu)).first;
-    return it->second;
-}
-
-// (Grid sizes are cached per host thread: rtw_render may be called from several threads at once.)
-// Fused path (L.wf_fuse & 1): one wf_step* kernel per iteration, then the tail
-// (on the compact LDS stage when L.wf_fuse & 2) and the reduce.
-//   clds > 0: compact nodes of all orders in LDS (wf_step_clds, 1024 threads)
-//   lds  > 0: the 32-B node array in LDS (wf_step<FEAT, true>)
-//   else    : the tree through L1/L2 (wf_step<FEAT, false>)
-// dynamic LDS of the fused kernels: tree stage + what is staged after it
-
-// scene classes whose fused step never runs on the compact LDS stage (wf_run: textured scenes keep the 32-B
-// stage), so wf_run_fused instantiates no compact-LDS kernel for them
-#define RTW_WF_NO_CLDS (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_MOVING | RTW_F_IMAGE | RTW_F_NOISE)
-template <uint32_t FEAT>
-void wf_run_fused(const rtw_launch& L, const rtw_wf& W0, hipStream_t st, int n_cu, size_t clds, size_t lds,
-                  rtw_timer* T) {
-    // (the fused steps' push cursors are static LDS on top of the dynamic sizes here: cur1 at 1024 threads, cur2 at 768)
-    constexpr size_t cur1 = RTW_WF_CURSOR_BYTES(1024u), cur2 = RTW_WF_CURSOR_BYTES(768u);
-    const size_t cdyn0 = clds,
-                 cdyn = cdyn0 + L.mat_lds + cur1 <= 160u * 1024u ? cdyn0 + L.mat_lds : cdyn0,
-                 ldyn = lds + (L.perlin_lds ? (size_t)L.n_perlin * RTW_PERLIN_BYTES : 0) +
-                        ((FEAT & RTW_F_GEOM) ? L.geom_lds : 0u) + L.shade_lds,
-                 tdyn = lds + ((FEAT & RTW_F_GEOM) ? L.geom_lds : 0u) + L.shade_lds,
-                 gdyn = wf_w2_lds<FEAT>(L);
-    thread_local uint64_t cgrid[2] = {0, 0}, tgrid[2] = {0, 0}, lgrid[2] = {0, 0}, ggrid[2] = {0, 0}, wtail[2] = {0, 0};
-    uint32_t grid = 0;
-    // The compact stage's block shape: the 8-copy stage (C2: 124 KB) leaves room for one 1024-thread block
-    // per CU; the 4-copy stage (L.n_orders == 4, 62 KB) for two 768-thread blocks (rtw_tuning.clds_shape 4)
-    // when it fits half the LDS
-    const bool y4 = L.n_orders == 4;
-    const int cn = L.cnode32 ? CN_F32_4 : y4 ? CN_F16_4 : CN_F16_8;
-    const uint32_t shape = clds && cn == CN_F16_4 && cdyn0 + cur2 <= RTW_WF_CLDS2_MAX && L.clds_shape == 4u ? 4u : 1u;
-    const bool two = shape == 4u;
-    const size_t cdyn2 = two && cdyn + cur2 > RTW_WF_CLDS2_MAX ? cdyn0 : cdyn;  // materials only if they fit too
-    const uint32_t cthreads = two ? 768u : 1024u;
-    if constexpr ((FEAT & RTW_WF_NO_CLDS) == 0) {
-        const uint64_t key = wf_key(n_cu, (uint32_t)cdyn2 | (shape << 24) | ((uint32_t)cn << 28));
-        if (clds && cgrid[1] != key) {
-            if (two) {
-                cgrid[0] = wf_grid(wf_step_clds2<FEAT, 768, 0>, n_cu, cdyn2, 768);
-                tgrid[0] = wf_grid(wf_tail_clds2<FEAT, 768, 0>, n_cu, clds, 768);
-            } else if (cn == CN_F32_4) {
-                cgrid[0] = wf_grid(wf_step_clds<FEAT, CN_F32_4>, n_cu, cdyn2, 1024);
-                tgrid[0] = wf_grid(wf_tail_clds<FEAT, CN_F32_4>, n_cu, clds, 1024);
-            } else if (cn == CN_F16_4) {
-                cgrid[0] = wf_grid(wf_step_clds<FEAT, CN_F16_4>, n_cu, cdyn2, 1024);
-                tgrid[0] = wf_grid(wf_tail_clds<FEAT, CN_F16_4>, n_cu, clds, 1024);
-            } else {
-                cgrid[0] = wf_grid(wf_step_clds<FEAT, CN_F16_8>, n_cu, cdyn2, 1024);
-                tgrid[0] = wf_grid(wf_tail_clds<FEAT, CN_F16_8>, n_cu, clds, 1024);
-            }
-            cgrid[1] = tgrid[1] = key;
-        }
-    }
-    if (clds) {
-        grid = (uint32_t)cgrid[0];
-    } else if (lds) {
-        if (lgrid[1] != wf_key(n_cu, ldyn)) {
-            lgrid[0] = wf_grid(wf_step<FEAT, true, 0>, n_cu, ldyn);
-            lgrid[1] = wf_key(n_cu, ldyn);
-        }
-        grid = (uint32_t)lgrid[0];
-    } else {
-        grid = wf_grid_cached(wf_step<FEAT, false, 0>, n_cu, gdyn, ggrid);
-    }
-    // iteration 0 appends to len[1]; every later iteration's output counters are
-    // zeroed by the kernel two iterations before (wf_step_zero_next)
-    (void)hipMemsetAsync(W0.len[1], 0, RTW_WF_STRIPES * RTW_WF_LEN_STRIDE * 4, st);
-    if (W0.deal) (void)hipMemsetAsync(W0.deal, 0, RTW_WF_DEAL_COUNTERS * 4, st);
-    rtw_wf W = wf_coherence(W0, grid * (clds ? cthreads / 64u : 4u), W0.sort_iters);
-    W.packed = wf_packed<FEAT>() ? 1u : 0u;  // the fused step and its tail: always the packed state
-    const uint32_t iters = L.max_depth < W.iters ? L.max_depth : W.iters;
-    rtw_wf Wt = W;  // the camera-ray lists serve the LDS-staged steps of static sphere scenes
-    if ((clds || lds) && iters) Wt = wf_lists<FEAT>(L, W, st);
-    else Wt.tl_count = nullptr;
-    // rayColor(depth <= 0) = 0 (camera.zig:183-185): no iteration writes W.ls, which holds the
-    // previous render's radiance, so the reduce must add zeros
-    if (iters == 0) (void)hipMemsetAsync(W.ls, 0, (size_t)W.n_paths * sizeof(rtw_rgb), st);
-    for (uint32_t it = 0; it < iters; it++) {
-        RTW_TIME_BEGIN(T, RTW_K_TRACE)
-        Wt.deal = W.deal;  // (only iteration 0 deals from it: counters 0 .. 511)
-        // deal bit 16: iteration it >= 1 claims its stripes' chunks from counters of its own
-        Wt.deal_it = (W.deal && (W.deal_mode & 16u) && it) ? W.deal + RTW_WF_DEAL_COUNTERS0 + it * RTW_WF_STRIPES
-                                                           : nullptr;
-        if constexpr ((FEAT & RTW_WF_NO_CLDS) == 0) {
-            if (clds) {
-                rtw_launch Lc = L;  // the materials are staged only when they fit
-                if (cdyn2 == cdyn0) Lc.mat_lds = 0;
-                if (two)
-                    {
-                        if (L.counters) hipLaunchKernelGGL((wf_step_clds2<FEAT, 768, 1>), dim3(grid), dim3(768), cdyn2, st, Lc, Wt, it);
-                        else if (RTW_STEP_IT0 && it == 0) hipLaunchKernelGGL((wf_step_clds2<FEAT, 768, 0, RTW_STEP_IT0 ? 1 : 2>), dim3(grid), dim3(768), cdyn2, st, Lc, Wt, it);
-                        else if (RTW_STEP_IT0) hipLaunchKernelGGL((wf_step_clds2<FEAT, 768, 0, RTW_STEP_IT0 ? 0 : 2>), dim3(grid), dim3(768), cdyn2, st, Lc, Wt, it);
-                        else hipLaunchKernelGGL((wf_step_clds2<FEAT, 768, 0>), dim3(grid), dim3(768), cdyn2, st, Lc, Wt, it);
-                    }
-                else if (cn == CN_F32_4)
-                    hipLaunchKernelGGL((wf_step_clds<FEAT, CN_F32_4>), dim3(grid), dim3(1024), cdyn2, st, Lc, Wt, it);
-                else if (cn == CN_F16_4)
-                    hipLaunchKernelGGL((wf_step_clds<FEAT, CN_F16_4>), dim3(grid), dim3(1024), cdyn2, st, Lc, Wt, it);
-                else
-                    hipLaunchKernelGGL((wf_step_clds<FEAT, CN_F16_8>), dim3(grid), dim3(1024), cdyn2, st, Lc, Wt, it);
-                RTW_TIME_END(T)
-                continue;
-            }
-        }
-        if (lds)
-            {
-                if (L.counters) hipLaunchKernelGGL((wf_step<FEAT, true, 1>), dim3(grid), dim3(256), ldyn, st, L, Wt, it);
-                else if (RTW_STEP_IT0 && it == 0) hipLaunchKernelGGL((wf_step<FEAT, true, 0, RTW_STEP_IT0 ? 1 : 2>), dim3(grid), dim3(256), ldyn, st, L, Wt, it);
-                else if (RTW_STEP_IT0) hipLaunchKernelGGL((wf_step<FEAT, true, 0, RTW_STEP_IT0 ? 0 : 2>), dim3(grid), dim3(256), ldyn, st, L, Wt, it);
-                else hipLaunchKernelGGL((wf_step<FEAT, true, 0>), dim3(grid), dim3(256), ldyn, st, L, Wt, it);
-            }
-        else
-            { if (L.counters) hipLaunchKernelGGL((wf_step<FEAT, false, 1>), dim3(grid), dim3(256), gdyn, st, L, W, it); else hipLaunchKernelGGL((wf_step<FEAT, false, 0>), dim3(grid), dim3(256), gdyn, st, L, W, it); }
-        RTW_TIME_END(T)
-    }
-    if (iters < L.max_depth) {
-        RTW_TIME_BEGIN(T, RTW_K_TAIL)
-        // one tail launch over iteration itx's queue (W's counters: the launch's own)
-        auto tail = [&](const rtw_wf& Wd, uint32_t itx) {
-            if constexpr ((FEAT & RTW_WF_NO_CLDS) == 0) {
-                if (clds && (L.wf_fuse & 2u)) {
-                    const rtw_wf& W = Wd;
-                    if (two)
-                        { if (L.counters) hipLaunchKernelGGL((wf_tail_clds2<FEAT, 768, 1>), dim3((uint32_t)tgrid[0]), dim3(768), clds, st, L, W, itx); else hipLaunchKernelGGL((wf_tail_clds2<FEAT, 768, 0>), dim3((uint32_t)tgrid[0]), dim3(768), clds, st, L, W, itx); }
-                    else if (cn == CN_F32_4)
-                        hipLaunchKernelGGL((wf_tail_clds<FEAT, CN_F32_4>), dim3((uint32_t)tgrid[0]), dim3(1024), clds, st, L, W, itx);
-                    else if (cn == CN_F16_4)
-                        hipLaunchKernelGGL((wf_tail_clds<FEAT, CN_F16_4>), dim3((uint32_t)tgrid[0]), dim3(1024), clds, st, L, W, itx);
-                    else
-                        hipLaunchKernelGGL((wf_tail_clds<FEAT, CN_F16_8>), dim3((uint32_t)tgrid[0]), dim3(1024), clds, st, L, W, itx);
-                    return;
-                }
-            }
-            if (lds && (L.wf_fuse & 2u)) {  // the node array in LDS for the tail too
-                thread_local uint64_t tl[2] = {0, 0};
-                if (tl[1] != wf_key(n_cu, tdyn)) {
-                    tl[0] = wf_grid(wf_tail_lds<FEAT, 0>, n_cu, tdyn);
-                    tl[1] = wf_key(n_cu, tdyn);
-                }
-                { if (L.counters) hipLaunchKernelGGL((wf_tail_lds<FEAT, 1>), dim3((uint32_t)tl[0]), dim3(256), tdyn, st, L, Wd, itx); else hipLaunchKernelGGL((wf_tail_lds<FEAT, 0>), dim3((uint32_t)tl[0]), dim3(256), tdyn, st, L, Wd, itx); }
-                return;
-            }
-            wf_launch_tail<FEAT>(L, Wd, st, n_cu, gdyn, wtail, itx);
-        };
-        rtw_wf Wd = W;  // the tail's input claims: counter 512 (iteration 0 took 0 .. 511)
-        if (W.deal) Wd.deal = W.deal + RTW_WF_DEAL_LAUNCH;
-        tail(Wd, iters);
-        RTW_TIME_END(T)
-    }
-    RTW_TIME_BEGIN(T, RTW_K_REDUCE)
-    hipLaunchKernelGGL(wf_reduce, dim3((W.n_pix + 255u) / 256u), dim3(256), 0, st, L, W);
-    RTW_TIME_END(T)
-}
-
-template <uint32_t FEAT>
-void wf_run(const rtw_launch& L, const rtw_wf& W0, hipStream_t st, int n_cu, rtw_timer* T) {
-    const WfGrids<FEAT> g = wf_grids<FEAT>(n_cu);
-    if (L.wf_fuse & 1u) {
-        size_t fclds = 0, flds = 0;
-        // (textured scenes keep the 32-B node stage: it leaves LDS for the Perlin tables and the
-        // 1024-thread compact kernel would spill at its 128-VGPR cap -- C5 -20 % measured)
-        if constexpr ((FEAT & (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_MOVING | RTW_F_IMAGE | RTW_F_NOISE)) == 0) {
-            const size_t c = (size_t)L.n_nodes * L.n_orders * (L.cnode32 ? 32u : 16u);
-            // (the stage and the fused step's push cursors)
-            if (L.cnodes && L.fast_box && L.wf_clds && c + RTW_WF_CURSOR_BYTES(1024u) <= RTW_WF_CLDS_MAX) fclds = c;
-        }
-        const size_t need = (size_t)L.n_nodes * L.n_orders * 32u;
-        if (!fclds && L.wf_lds && need <= RTW_WF_LDS_MAX) flds = (need + 511u) / 512u * 512u;
-        // measured: fused wins on C2 (+8.5 %), C5 (+24 %), Cornell (+2 %) and, since the
-        // round-3 queues and object trees, Cornell smoke (media: +23 %); through L1/L2 (C4, RTW_WF_FUSE
-        // bit 2) it loses (-13 %)
-        if ((fclds || flds) || (L.wf_fuse & 4u)) {
-            wf_run_fused<FEAT>(L, W0, st, n_cu, fclds, flds, T);
-            return;
-        }
-    }
-    rtw_wf W = wf_coherence(W0, g.shade * 4u, W0.sort_iters_split);  // the split kernels' queues
-    W.packed = wf_packed<FEAT>() ? 1u : 0u;  // the split kernels (and their tail) use the packed state too
-    const rtw_wf W1 = W;
-    // dynamic deal: iteration 0's trace deals from counters 0 .. 511, its shade from 512 .. 1023
-    if (W0.deal) (void)hipMemsetAsync(W0.deal, 0, RTW_WF_DEAL_COUNTERS * 4, st);
-    const uint32_t iters = L.max_depth < W.iters ? L.max_depth : W.iters;
-    // iteration 0's trace and shade generate the camera rays themselves (wf_camera); with no
-    // iteration (max_depth 0) nothing writes W.ls and the reduce must add zeros
-    if (iters == 0) (void)hipMemsetAsync(W.ls, 0, (size_t)W.n_paths * sizeof(rtw_rgb), st);
-    const rtw_wf Wt = iters ? wf_lists<FEAT>(L, W, st) : W;  // camera rays: iteration 0 of wf_trace (L1/L2)
-    rtw_wf Ws0 = W;  // iteration 0's shade: its own counters
-    if (W.deal) Ws0.deal = W.deal + RTW_WF_DEAL_LAUNCH;
-    const size_t w2l = wf_w2_lds<FEAT>(L);  // the two-wide walk's stacks (trace / tail through L1/L2)
-    thread_local uint64_t wtrace[2] = {0, 0}, wtrace0[2] = {0, 0}, wtail[2] = {0, 0};
-    const size_t lds_need = (size_t)L.n_nodes * L.n_orders * 32u;
-    const size_t lds = (L.wf_lds && lds_need <= RTW_WF_LDS_MAX)
-                           ? (lds_need + 511u) / 512u * 512u : 0;
-    const size_t tlds = lds ? lds + ((FEAT & RTW_F_GEOM) ? L.geom_lds : 0u) : 0;  // + quads/members/instances
-    const uint32_t lds_grid = lds ? wf_lds_grid<FEAT, false>(n_cu, tlds) : 0,
-                   lds_grid0 = lds ? wf_lds_grid<FEAT, true>(n_cu, tlds) : 0;
-    // compact nodes of every octant copy in LDS (small static sphere trees)
-    const size_t clds = (L.cnodes && L.fast_box && L.wf_clds)
-                            ? (size_t)L.n_nodes * L.n_orders * (L.cnode32 ? 32u : 16u) : 0;
-    thread_local uint64_t clds_grid_cache[3] = {0, 0, 0};
-    uint32_t clds_grid = 0, clds_grid0 = 0;
-    constexpr uint32_t clds_threads = 1024;  // one block per CU shares the stage (256 / 512: slower)
-    if constexpr ((FEAT & (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_MOVING)) == 0) {
-        if (clds && clds <= RTW_WF_CLDS_MAX) {
-            if (clds_grid_cache[1] != wf_key(n_cu, clds)) {  // (the Y4 forms: the same registers)
-                clds_grid_cache[0] = wf_grid(wf_trace_clds<FEAT>, n_cu, clds, clds_threads);
-                clds_grid_cache[2] = wf_grid(wf_trace_clds<FEAT, true>, n_cu, clds, clds_threads);
-                clds_grid_cache[1] = wf_key(n_cu, clds);
-            }
-            clds_grid = (uint32_t)clds_grid_cache[0];
-            clds_grid0 = (uint32_t)clds_grid_cache[2];
-        }
-    }
-    for (uint32_t it = 0; it < iters; it++) {
-        RTW_TIME_BEGIN(T, RTW_K_TRACE)
-        // deal bit 16: iteration it >= 1's trace and shade claim their stripes' chunks from counters of their own
-        rtw_wf W = W1;
-        rtw_wf Ws = W1;
-        if (W1.deal && (W1.deal_mode & 16u) && it) {
-            W.deal_it = W1.deal + RTW_WF_DEAL_COUNTERS0 + it * RTW_WF_STRIPES;
-            Ws.deal_it = W1.deal + RTW_WF_DEAL_SHADE + it * RTW_WF_STRIPES;
-        }
-        if constexpr ((FEAT & (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_MOVING)) == 0) {
-            if (clds_grid) {
-                const int cn = L.cnode32 ? CN_F32_4 : L.n_orders == 4 ? CN_F16_4 : CN_F16_8;
-                const dim3 g(it == 0 ? clds_grid0 : clds_grid), b(clds_threads);
-                if (it == 0 && cn == CN_F32_4) hipLaunchKernelGGL((wf_trace_clds<FEAT, true, CN_F32_4>), g, b, clds, st, L, W, it);
-                else if (it == 0 && cn == CN_F16_4) hipLaunchKernelGGL((wf_trace_clds<FEAT, true, CN_F16_4>), g, b, clds, st, L, W, it);
-                else if (it == 0) hipLaunchKernelGGL((wf_trace_clds<FEAT, true, CN_F16_8>), g, b, clds, st, L, W, it);
-                else if (cn == CN_F32_4) hipLaunchKernelGGL((wf_trace_clds<FEAT, false, CN_F32_4>), g, b, clds, st, L, W, it);
-                else if (cn == CN_F16_4) hipLaunchKernelGGL((wf_trace_clds<FEAT, false, CN_F16_4>), g, b, clds, st, L, W, it);
-                else hipLaunchKernelGGL((wf_trace_clds<FEAT, false, CN_F16_8>), g, b, clds, st, L, W, it);
-                RTW_TIME_END(T)
-                goto shade_step;
-            }
-        }
-        if (lds && it == 0)
-            hipLaunchKernelGGL((wf_trace<FEAT, true, true>), dim3(lds_grid0), dim3(256), tlds, st, L, W, it);
-        else if (lds)
-            hipLaunchKernelGGL((wf_trace<FEAT, true>), dim3(lds_grid), dim3(256), tlds, st, L, W, it);
-        else if (it == 0)
-            hipLaunchKernelGGL((wf_trace<FEAT, false, true>),
-                               dim3(wf_grid_cached(wf_trace<FEAT, false, true>, n_cu, w2l, wtrace0)), dim3(256), w2l, st,
-                               L, Wt, it);
-        else
-            hipLaunchKernelGGL((wf_trace<FEAT, false>), dim3(wf_grid_cached(wf_trace<FEAT, false>, n_cu, w2l, wtrace)),
-                               dim3(256), w2l, st, L, W, it);
-        RTW_TIME_END(T)
-    shade_step:
-        RTW_TIME_BEGIN(T, RTW_K_SHADE)
-        if (it == 0)
-            hipLaunchKernelGGL((wf_shade<FEAT, true>), dim3(g.shade0), dim3(256), (FEAT & RTW_F_GEOM) ? L.geom_lds : 0u,
-                               st, L, Ws0, it);
-        else
-            hipLaunchKernelGGL(wf_shade<FEAT>, dim3(g.shade), dim3(256), (FEAT & RTW_F_GEOM) ? L.geom_lds : 0u, st, L,
-                               Ws, it);
-        RTW_TIME_END(T)
-    }
-    if (iters < L.max_depth) {
-        RTW_TIME_BEGIN(T, RTW_K_TAIL)
-        rtw_wf Wd = W;  // the tail's input claims: counter 1024 (iteration 0's trace and shade took 0 .. 1023)
-        if (W.deal) Wd.deal = W.deal + 2 * RTW_WF_DEAL_LAUNCH;
-        auto tail = [&](const rtw_wf& Wx, uint32_t itx) {
-            if (lds && (L.wf_fuse & 2u)) {  // the node array (+ geometry) in LDS for the tail (smoke +5 %)
-                thread_local uint64_t tl[2] = {0, 0};
-                const size_t tdyn = tlds + L.shade_lds;  // wf_tail_lds stages the materials too
-                if (tl[1] != wf_key(n_cu, tdyn)) {
-                    tl[0] = wf_grid(wf_tail_lds<FEAT, 0>, n_cu, tdyn);
-                    tl[1] = wf_key(n_cu, tdyn);
-                }
-                { if (L.counters) hipLaunchKernelGGL((wf_tail_lds<FEAT, 1>), dim3((uint32_t)tl[0]), dim3(256), tdyn, st, L, Wx, itx); else hipLaunchKernelGGL((wf_tail_lds<FEAT, 0>), dim3((uint32_t)tl[0]), dim3(256), tdyn, st, L, Wx, itx); }
-            } else {
-                wf_launch_tail<FEAT>(L, Wx, st, n_cu, w2l, wtail, itx);
-            }
-        };
-        tail(Wd, iters);
-        RTW_TIME_END(T)
-    }
-    RTW_TIME_BEGIN(T, RTW_K_REDUCE)
-    hipLaunchKernelGGL(wf_reduce, dim3((W.n_pix + 255u) / 256u), dim3(256), 0, st, L, W);
-    RTW_TIME_END(T)
-}
-
-// Object scenes without media, image / noise textures or motion (quads, instances, lights,
-// solid / checker textures: the Cornell box, HEAD's default scene) get their own
-// instantiation: without the unused code paths the fused step needs fewer registers.
-// Likewise static, unlit sphere scenes with image / noise textures (BASELINE config 5) and
-// object scenes with media but no image / noise textures or motion (Cornell smoke).
-#define RTW_F_OBJECTS (RTW_F_GEOM | RTW_F_LIGHT | RTW_F_CHECKER)
-#define RTW_F_TEXTURED (RTW_F_CHECKER | RTW_F_IMAGE | RTW_F_NOISE)
-#define RTW_F_MEDIA (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_LIGHT | RTW_F_CHECKER)
-uint32_t wf_pick_feat(uint32_t f) {
-    // vertex attributes registered (rtw_feat_of): their two instantiations, on top of every feature and the
-    // instance trees (a scene without a tree runs them too: inst_hit_t falls back to the member loop)
-    if (f & RTW_F_ATTR) return RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR | (f & RTW_F_PDF);
-    // lights registered (rtw_feat_of): the mixture-density instantiations, on top of every feature
-    if (f & RTW_F_PDF) return (f & RTW_F_TREE) ? (RTW_F_ALL | RTW_F_TREE | RTW_F_PDF) : (RTW_F_ALL | RTW_F_PDF);
-    if (f & RTW_F_TREE) return RTW_F_ALL | RTW_F_TREE;  // instance trees (inst_tree_t): their own instantiation
-    if ((f & ~RTW_F_CHECKER) == 0) return f ? RTW_F_CHECKER : 0u;
-    if ((f & RTW_F_GEOM) && (f & ~RTW_F_OBJECTS) == 0) return RTW_F_OBJECTS;
-    if ((f & ~RTW_F_TEXTURED) == 0) return RTW_F_TEXTURED;
-    if ((f & RTW_F_MEDIUM) && (f & ~RTW_F_MEDIA) == 0) return RTW_F_MEDIA;
-    return (f & (RTW_F_GEOM | RTW_F_MEDIUM)) ? RTW_F_ALL : RTW_F_SPHERES;
-}
-
 }  // namespace
 
-#if defined(RTW_WF_ATTRS_TU)
-// contexts with registered vertex attributes (rtw_feat_of: RTW_F_ATTR) run from rtw_wavefront_attrs.hip
-void rtw_wf_run_attrs(const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, rtw_timer* T, bool pdf) {
-    if (pdf) wf_run<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>(L, W, st, n_cu, T);
-    else wf_run<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR>(L, W, st, n_cu, T);
-}
-
-// (waves of the 256-thread shade grids, as rtw_wavefront_max_waves counts the other classes')
-uint32_t rtw_wf_attrs_max_waves(int n_cu) {
-    uint32_t m = 0;
-    auto mx = [&m](uint32_t a, uint32_t b) { m = std::max({m, a, b}); };
-    mx(wf_grids<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR>(n_cu).shade, wf_grids<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR>(n_cu).shade0);
-    mx(wf_grids<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>(n_cu).shade,
-       wf_grids<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>(n_cu).shade0);
-    return 4 * m;
-}
-#elif defined(RTW_WF_LIGHTS_TU)
-// contexts with registered lights (rtw_feat_of: RTW_F_PDF) run from rtw_wavefront_lights.hip
-void rtw_wf_run_lights(const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, rtw_timer* T, bool tree) {
-    if (tree) wf_run<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF>(L, W, st, n_cu, T);
-    else wf_run<RTW_F_ALL | RTW_F_PDF>(L, W, st, n_cu, T);
-}
-
-// (waves of the 256-thread shade grids, as rtw_wavefront_max_waves counts the other classes')
-uint32_t rtw_wf_lights_max_waves(int n_cu) {
-    uint32_t m = 0;
-    auto mx = [&m](uint32_t a, uint32_t b) { m = std::max({m, a, b}); };
-    mx(wf_grids<RTW_F_ALL | RTW_F_PDF>(n_cu).shade, wf_grids<RTW_F_ALL | RTW_F_PDF>(n_cu).shade0);
-    mx(wf_grids<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF>(n_cu).shade, wf_grids<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF>(n_cu).shade0);
-    return 4 * m;
-}
-#elif !defined(RTW_WF_SPHERES_TU)
-// untextured static sphere scenes (FEAT 0 / CHECKER: BASELINE C2, C3, C4) run from rtw_wavefront_spheres.hip,
-// this code compiled with 64-B loop alignment (csrc/Makefile): C2 +0.8 %, C3 +0.7 %; the other scene classes
-// gained nothing from the flag (C5 -0.3 %, Cornell -0.4 %), so they keep the default placement
-void rtw_wf_run_spheres(const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, rtw_timer* T, uint32_t feat);
-uint32_t rtw_wf_spheres_max_waves(int n_cu);
-// contexts with registered lights (the RTW_F_PDF instantiations) from rtw_wavefront_lights.hip
-void rtw_wf_run_lights(const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, rtw_timer* T, bool tree);
-uint32_t rtw_wf_lights_max_waves(int n_cu);
-// contexts with registered vertex attributes (the RTW_F_ATTR instantiations) from rtw_wavefront_attrs.hip
-void rtw_wf_run_attrs(const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, rtw_timer* T, bool pdf);
-uint32_t rtw_wf_attrs_max_waves(int n_cu);
-
-void rtw_wavefront_batch(const rtw_launch& L, const rtw_wf& W, void* stream, int n_cu, rtw_timer* T) {
-    hipStream_t st = (hipStream_t)stream;
-    switch (wf_pick_feat(rtw_feat_of(L))) {
-    case RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR: rtw_wf_run_attrs(L, W, st, n_cu, T, false); break;
-    case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR: rtw_wf_run_attrs(L, W, st, n_cu, T, true); break;
-    case RTW_F_ALL | RTW_F_PDF: rtw_wf_run_lights(L, W, st, n_cu, T, false); break;
-    case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF: rtw_wf_run_lights(L, W, st, n_cu, T, true); break;
-    case 0u: rtw_wf_run_spheres(L, W, st, n_cu, T, 0u); break;
-    case RTW_F_CHECKER: rtw_wf_run_spheres(L, W, st, n_cu, T, RTW_F_CHECKER); break;
-    case RTW_F_SPHERES: wf_run<RTW_F_SPHERES>(L, W, st, n_cu, T); break;
-    case RTW_F_OBJECTS: wf_run<RTW_F_OBJECTS>(L, W, st, n_cu, T); break;
-    case RTW_F_TEXTURED: wf_run<RTW_F_TEXTURED>(L, W, st, n_cu, T); break;
-    case RTW_F_MEDIA: wf_run<RTW_F_MEDIA>(L, W, st, n_cu, T); break;
-    case RTW_F_ALL | RTW_F_TREE: wf_run<RTW_F_ALL | RTW_F_TREE>(L, W, st, n_cu, T); break;
-    default: wf_run<RTW_F_ALL>(L, W, st, n_cu, T); break;
-    }
-}
-
-uint32_t rtw_wavefront_max_waves(int n_cu) {
-    uint32_t m = 0;
-    auto mx = [&m](uint32_t a, uint32_t b) { m = std::max({m, a, b}); };
-    mx(wf_grids<RTW_F_SPHERES>(n_cu).shade, wf_grids<RTW_F_SPHERES>(n_cu).shade0);
-    mx(wf_grids<RTW_F_OBJECTS>(n_cu).shade, wf_grids<RTW_F_OBJECTS>(n_cu).shade0);
-    mx(wf_grids<RTW_F_TEXTURED>(n_cu).shade, wf_grids<RTW_F_TEXTURED>(n_cu).shade0);
-    mx(wf_grids<RTW_F_MEDIA>(n_cu).shade, wf_grids<RTW_F_MEDIA>(n_cu).shade0);
-    mx(wf_grids<RTW_F_ALL>(n_cu).shade, wf_grids<RTW_F_ALL>(n_cu).shade0);
-    mx(wf_grids<RTW_F_ALL | RTW_F_TREE>(n_cu).shade, wf_grids<RTW_F_ALL | RTW_F_TREE>(n_cu).shade0);
-    return std::max({4 * m, rtw_wf_spheres_max_waves(n_cu), rtw_wf_lights_max_waves(n_cu), rtw_wf_attrs_max_waves(n_cu)});
-}
-#else
-void rtw_wf_run_spheres(const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, rtw_timer* T, uint32_t feat) {
-    if (feat) wf_run<RTW_F_CHECKER>(L, W, st, n_cu, T);
-    else wf_run<0u>(L, W, st, n_cu, T);
-}
-
-// (waves: the 256-thread shade grids and the compact-LDS kernels' grids, whichever launches more; computed per
-// CU count -- it sizes the stripes, which the kernels do not bound-check)
-uint32_t rtw_wf_spheres_max_waves(int n_cu) {
-    static std::mutex mu;
-    static std::map<int, uint32_t> cache;
-    std::lock_guard<std::mutex> lk(mu);
-    if (auto it = cache.find(n_cu); it != cache.end()) return it->second;
-    const uint32_t b = std::max({wf_grids<0u>(n_cu).shade, wf_grids<0u>(n_cu).shade0, wf_grids<RTW_F_CHECKER>(n_cu).shade,
-                                 wf_grids<RTW_F_CHECKER>(n_cu).shade0});
-    const uint32_t c2 = std::max(wf_grid(wf_step_clds2<0u, 768, 0>, n_cu, 0, 768), wf_grid(wf_step_clds2<RTW_F_CHECKER, 768, 0>, n_cu, 0, 768)) * 12u;
-    const uint32_t c1 = std::max(wf_grid(wf_step_clds<0u>, n_cu, 0, 1024), wf_grid(wf_step_clds<RTW_F_CHECKER>, n_cu, 0, 1024)) * 16u;
-    const uint32_t val = std::max({4u * b, c2, c1});
-    cache[n_cu] = val;
-    return val;
-}
-
-#if defined(RTW_DIAG_WALK)  // (the sphere-scene kernels' records and counters: this translation unit's)
-// diagnostic build only: where the per-slot walk records of iteration `it` go (null: off)
-extern "C" int rtw_debug_walk_records(void* d_rec, uint32_t cap_slots, uint32_t it) {
-    uint4* p = static_cast<uint4*>(d_rec);
-    if (hipMemcpyToSymbol(HIP_SYMBOL(rtw_diag_rec), &p, sizeof p) != hipSuccess) return RTW_E_HIP;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(rtw_diag_rec_cap), &cap_slots, 4) != hipSuccess) return RTW_E_HIP;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(rtw_diag_rec_it), &it, 4) != hipSuccess) return RTW_E_HIP;
-    return RTW_OK;
-}
-// diagnostic build only: the compact walk's step counters (rtw_device.h WalkDiag), read and optionally reset
-extern "C" int rtw_debug_walk_counters(uint64_t* out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rtw_diag_walk), 16 * sizeof(uint64_t)) != hipSuccess) return RTW_E_HIP;
-    if (reset) {
-        const uint64_t z[16] = {0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(rtw_diag_walk), z, sizeof z) != hipSuccess) return RTW_E_HIP;
-    }
-    return RTW_OK;
-}
-#endif
-#endif  // RTW_WF_SPHERES_TU
+#include "rtw_wavefront_dispatch.h"  // the host side: grids, staging plan, launches, class tables
