@@ -22,53 +22,53 @@
 #include "rtw_device.h"
 #include "rtw_wavefront.h"
 
+namespace {
+// Pixels [a, b) of a chunk with the sample loop of class F (rtw_with_class: the instantiation the GPU kernels run)
+template <uint32_t F>
+void cpu_pixels(const rtw_launch& L, uint32_t a, uint32_t b, float* out, const rtw_render_opts* stop,
+                std::atomic<bool>& stopped) {
+    Counters cnt;
+    for (uint32_t i = a; i < b; i++) {
+        if (rtw_stop_requested(stop)) {  // polled per pixel, as Camera.render polls `running` (camera.zig:107)
+            stopped = true;
+            return;
+        }
+        const uint32_t x = i % L.W;
+        uint32_t y = i / L.W;
+        if (L.n_shards && !map_row(L, y, y)) continue;  // a shard's logical row -> image row (rows past H: none)
+        if (y >= L.H) continue;
+        const uint32_t pixel = y * L.W + x;
+        float* px = out + 4 * (size_t)i;
+        float r = px[0], g = px[1], bl = px[2];
+        for (uint32_t s = L.s0; s < L.s1; s++) {
+            const f3 c = sample_radiance<F>(L.nodes, L, pixel, x + L.pixel_offset, y + L.pixel_offset, s, cnt);
+            r += c.x;
+            g += c.y;
+            bl += c.z;
+        }
+        px[0] = r;
+        px[1] = g;
+        px[2] = bl;
+        px[3] = (float)L.s1;  // writeColor: number_of_samples (camera.zig:56)
+    }
+}
+}  // namespace
+
 int rtw_cpu_render(const rtw_launch& L, uint32_t begin, uint32_t end, float* out, uint32_t threads,
                    const rtw_render_opts* stop) {
     const uint32_t n = end - begin;
     if (threads == 0) threads = std::max(1u, std::thread::hardware_concurrency());
     threads = std::min<uint32_t>(threads, std::max(1u, n));
     std::atomic<bool> stopped{false};
-    const bool tree = (L.feat & RTW_F_TREE) != 0;  // instance trees: the instantiation the GPU kernels run
-    const bool pdf = L.n_lights != 0;
-    const bool attr = L.vattrs != nullptr;  // vertex attributes registered: their instantiations (always with the trees')
+    // the class once per call: instance trees, registered lights (the mixture-density instantiations) and vertex
+    // attributes (always with the trees') select it as they do on the GPU
+    decltype(&cpu_pixels<RTW_F_ALL>) pixels = nullptr;
+    rtw_with_class<false>(rtw_feat_of(L), [&](auto c) { pixels = cpu_pixels<decltype(c)::value>; });
     // contiguous chunks, as startRender's Tasks (main.zig:318-324); samples in order per pixel
     auto work = [&](uint32_t t) {
         const uint32_t a = begin + (uint32_t)((uint64_t)n * t / threads);
         const uint32_t b = begin + (uint32_t)((uint64_t)n * (t + 1) / threads);
-        Counters cnt;
-        for (uint32_t i = a; i < b; i++) {
-            if (rtw_stop_requested(stop)) {  // polled per pixel, as Camera.render polls `running` (camera.zig:107)
-                stopped = true;
-                return;
-            }
-            const uint32_t x = i % L.W;
-            uint32_t y = i / L.W;
-            if (L.n_shards && !map_row(L, y, y)) continue;  // a shard's logical row -> image row (rows past H: none)
-            if (y >= L.H) continue;
-            const uint32_t pixel = y * L.W + x;
-            float* px = out + 4 * (size_t)i;
-            float r = px[0], g = px[1], bl = px[2];
-            for (uint32_t s = L.s0; s < L.s1; s++) {
-                const uint32_t px = x + L.pixel_offset, py = y + L.pixel_offset;
-                f3 c;
-                if (attr)
-                    c = pdf ? sample_radiance<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>(L.nodes, L, pixel, px, py, s, cnt)
-                            : sample_radiance<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR>(L.nodes, L, pixel, px, py, s, cnt);
-                else if (pdf)  // lights registered: the mixture-density instantiations
-                    c = tree ? sample_radiance<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF>(L.nodes, L, pixel, px, py, s, cnt)
-                             : sample_radiance<RTW_F_ALL | RTW_F_PDF>(L.nodes, L, pixel, px, py, s, cnt);
-                else
-                    c = tree ? sample_radiance<RTW_F_ALL | RTW_F_TREE>(L.nodes, L, pixel, px, py, s, cnt)
-                             : sample_radiance<RTW_F_ALL>(L.nodes, L, pixel, px, py, s, cnt);
-                r += c.x;
-                g += c.y;
-                bl += c.z;
-            }
-            px[0] = r;
-            px[1] = g;
-            px[2] = bl;
-            px[3] = (float)L.s1;  // writeColor: number_of_samples (camera.zig:56)
-        }
+        pixels(L, a, b, out, stop, stopped);
     };
     std::vector<std::thread> pool;
     pool.reserve(threads);
@@ -80,8 +80,8 @@ int rtw_cpu_render(const rtw_launch& L, uint32_t begin, uint32_t end, float* out
 
 // ABI 6 test hook (include/rtw_gpu.h): the walk's sphere fast-reject against Sphere.hit's exact accept, on
 // the host -- sphere_may_hit is the device's code (rtw_device.h), the same fp32 operations
-extern "C" int rtw_debug_sphere_filter(uint32_t n, const float* a, const float* half_b, const float* c, const float* closest,
-                            uint8_t* may_hit, uint8_t* accept) {
+extern "C" int rtw_debug_sphere_filter(uint32_t n, const float* a, const float* half_b, const float* c,
+                                       const float* closest, uint8_t* may_hit, uint8_t* accept) {
     if (n && (!a || !half_b || !c || !closest || !may_hit || !accept)) return RTW_E_INVALID;
     for (uint32_t i = 0; i < n; i++) {
         // the ray constants as ray_trav derives them from a (fast_reject on)
@@ -146,8 +146,9 @@ extern "C" int rtw_debug_quad_hit(uint32_t n, const rtw_quad* quads, const float
 
 // Host-only test hook (include/rtw_gpu.h), and the symbol a caller detects vertex attributes by: the hit record of
 // (record, attribute, ray, t) -- rtw_quad_init, quad_prep and quad_attr, the device's code, the same fp32 operations
-extern "C" int rtw_debug_quad_shade(uint32_t n, const rtw_quad* quads, const rtw_vertex_attr* attrs, const float* origins,
-                                    const float* dirs, const float* t, float* normal, float* uv, uint8_t* front) {
+extern "C" int rtw_debug_quad_shade(uint32_t n, const rtw_quad* quads, const rtw_vertex_attr* attrs,
+                                    const float* origins, const float* dirs, const float* t, float* normal, float* uv,
+                                    uint8_t* front) {
     if (n && (!quads || !attrs || !origins || !dirs || !t || !normal || !uv || !front)) return RTW_E_INVALID;
     char msg[96];
     for (uint32_t i = 0; i < n; i++) {
@@ -157,7 +158,8 @@ extern "C" int rtw_debug_quad_shade(uint32_t n, const rtw_quad* quads, const rtw
             return RTW_E_INVALID;
         }
         if (attrs[i].flags & ~(uint32_t)(RTW_ATTR_NORMALS | RTW_ATTR_UVS)) {
-            std::snprintf(msg, sizeof msg, "rtw_debug_quad_shade: attribute %u: unknown flag bits 0x%x", i, attrs[i].flags);
+            std::snprintf(msg, sizeof msg, "rtw_debug_quad_shade: attribute %u: unknown flag bits 0x%x", i,
+                          attrs[i].flags);
             rtw_set_error(msg);
             return RTW_E_INVALID;
         }
@@ -165,7 +167,8 @@ extern "C" int rtw_debug_quad_shade(uint32_t n, const rtw_quad* quads, const rtw
         rtw_quad_init(quads[i], q);
         rtw_vertex_attr a = attrs[i];
         if ((a.flags & RTW_ATTR_NORMALS) && !rtw_vattr_normalise(attrs[i], a)) {
-            std::snprintf(msg, sizeof msg, "rtw_debug_quad_shade: attribute %u: a normal is not finite or has zero length", i);
+            std::snprintf(msg, sizeof msg, "rtw_debug_quad_shade: attribute %u: a normal is not finite or has zero "
+                          "length", i);
             rtw_set_error(msg);
             return RTW_E_INVALID;
         }

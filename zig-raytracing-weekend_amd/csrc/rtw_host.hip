@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -44,6 +45,11 @@ void rtw_set_error(const char* msg) { g_err = msg ? msg : ""; }
 // struct rtw_ctx: see rtw_internal.h
 
 namespace {
+// the material kinds that read a texture
+bool textured(const rtw_material& m) {
+    return m.kind == RTW_MAT_LAMBERTIAN || m.kind == RTW_MAT_DIFFUSE_LIGHT || m.kind == RTW_MAT_ISOTROPIC;
+}
+
 uint32_t scene_features(const rtw_scene_desc* d) {
     uint32_t f = 0;
     for (uint32_t i = 0; i < d->n_spheres; i++)
@@ -51,14 +57,451 @@ uint32_t scene_features(const rtw_scene_desc* d) {
     for (uint32_t i = 0; i < d->n_materials; i++) {
         const rtw_material& m = d->materials[i];
         if (m.kind == RTW_MAT_DIFFUSE_LIGHT || m.kind == RTW_MAT_ISOTROPIC) f |= RTW_F_LIGHT;
-        const bool textured = m.kind == RTW_MAT_LAMBERTIAN || m.kind == RTW_MAT_DIFFUSE_LIGHT || m.kind == RTW_MAT_ISOTROPIC;
-        if (!textured) continue;
+        if (!textured(m)) continue;
         const uint32_t k = d->textures[m.texture].kind;
         if (k == RTW_TEX_CHECKER) f |= RTW_F_CHECKER;
         if (k == RTW_TEX_IMAGE) f |= RTW_F_IMAGE;
         if (k == RTW_TEX_NOISE) f |= RTW_F_NOISE;
     }
     return f;
+}
+
+// ---- scene creation (rtw_scene_create_ex), step by step ----
+
+int check_tuning(const rtw_tuning& tu) {
+    if (tu.kernel > RTW_KERNEL_SIMPLE) return fail(RTW_E_INVALID, "tuning.kernel out of range");
+    if (tu.bvh_orders != 0 && tu.bvh_orders != 1 && tu.bvh_orders != 4 && tu.bvh_orders != 8)
+        return fail(RTW_E_INVALID, "tuning.bvh_orders must be 0, 1, 4 or 8");
+    if (tu.clds_shape != 0 && tu.clds_shape != 1 && tu.clds_shape != 4)
+        return fail(RTW_E_INVALID, "tuning.clds_shape must be 0, 1 or 4 (ABI 8)");
+    if (tu.deal & ~(uint32_t)RTW_DEAL_ALL)
+        return fail(RTW_E_INVALID, "tuning.deal: bits 1 | 2 | 8 | 16 | 32 | 128 (RTW_DEAL_*)");
+    if (tu.wf_iters > RTW_WF_MAX_ITERS) return fail(RTW_E_INVALID, "tuning.wf_iters out of range");
+    if ((tu.object_tree & 0xFFu) > 100 || (tu.object_tree & ~(0xFFu | RTW_OTREE_NO_CULL)))
+        return fail(RTW_E_INVALID, "tuning.object_tree: 0..100 [| RTW_OTREE_NO_CULL]");
+    if (tu.sort_bits > RTW_WF_BUCKET_BITS) return fail(RTW_E_INVALID, "tuning.sort_bits out of range");
+    if (tu.mega_shade_min < 1 || tu.mega_shade_min > 64)
+        return fail(RTW_E_INVALID, "tuning.mega_shade_min out of range");
+    if (tu.mega_waves != 1 && tu.mega_waves != 6 && tu.mega_waves != 8)
+        return fail(RTW_E_INVALID, "tuning.mega_waves must be 1, 6 or 8");
+    if (tu.wf_paths && tu.wf_paths < 4096) return fail(RTW_E_INVALID, "tuning.wf_paths must be 0 or >= 4096");
+    return RTW_OK;
+}
+
+// the description lists something to render (rtw_scene_create_ex, rtw_scene_flatten)
+bool has_objects(const rtw_scene_desc* d) {
+    return !(d->n_spheres && !d->spheres) && (d->objects ? d->n_objects : d->n_spheres) != 0;
+}
+
+int check_desc(const rtw_scene_desc* d) {
+    if (!has_objects(d)) return fail(RTW_E_INVALID, "scene has no objects");
+    if (d->n_materials == 0 || !d->materials) return fail(RTW_E_INVALID, "scene has no materials");
+    for (uint32_t i = 0; i < d->n_spheres; i++)
+        if (d->spheres[i].material >= d->n_materials) return fail(RTW_E_INVALID, "sphere material index out of range");
+    for (uint32_t i = 0; i < d->n_materials; i++) {
+        const rtw_material& m = d->materials[i];
+        if (m.kind > RTW_MAT_ISOTROPIC) return fail(RTW_E_INVALID, "unknown material kind");
+        if (textured(m) && m.texture >= d->n_textures)
+            return fail(RTW_E_INVALID, "material texture index out of range");
+    }
+    for (uint32_t i = 0; i < d->n_textures; i++) {
+        const rtw_texture& t = d->textures[i];
+        if (t.kind > RTW_TEX_NOISE) return fail(RTW_E_INVALID, "unknown texture kind");
+        if (t.kind == RTW_TEX_IMAGE && t.image >= d->n_images)
+            return fail(RTW_E_INVALID, "texture image index out of range");
+        if (t.kind == RTW_TEX_NOISE && t.perlin >= d->n_perlins)
+            return fail(RTW_E_INVALID, "texture perlin index out of range");
+    }
+    for (uint32_t i = 0; d->quads && i < d->n_quads; i++)
+        if (d->quads[i].shape > RTW_QUAD_TRIANGLE) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "quad %u: unknown shape %u (RTW_QUAD_PARALLELOGRAM = 0 or "
+                          "RTW_QUAD_TRIANGLE = 1)", i, d->quads[i].shape);
+            return fail(RTW_E_INVALID, msg);
+        }
+    for (uint32_t i = 0; i < d->n_images; i++) {
+        const rtw_image& im = d->images[i];
+        if (im.width && im.height && (!im.data || im.bytes_per_row < 4 * im.width))
+            return fail(RTW_E_INVALID, "bad image");
+    }
+    return RTW_OK;
+}
+
+// SAH trees of sphere scenes: 8 octant-ordered copies of the node array (tuning.bvh_orders 4: copies by the
+// x and z signs; 1: one, ordered along order_dir).  Scenes with quads/instances/media keep one order: their leaf
+// tests are costly, and lanes walking different orders stop executing them together (Cornell: -31 % with 8 orders).
+uint32_t choose_orders(const rtw_scene_desc* d, const rtw_tuning& tu, uint32_t sfeat, bool objects) {
+    uint32_t orders = (d->bvh_mode == RTW_BVH_SAH && !objects) ? 8u : 1u;
+    // Round 5: small static untextured sphere trees (Book-1, C2 / C3) take 4 copies (x, z signs): their compact
+    // stage (+ materials) then fits half the LDS and the fused step and tail run two 768-thread blocks per CU, 6
+    // waves per SIMD (C2 +4.6 %, profiles/r5_stage/).  (A tree of ~2 nodes per sphere; the check is redone on the
+    // built tree by the launcher, which falls back to one block.)
+    const size_t mat_b = (size_t)d->n_materials * sizeof(rtw_dev_material);
+    if (orders == 8 && !tu.bvh_orders && tu.compact_nodes == 1 && tu.fast_box && !(sfeat & ~RTW_F_CHECKER) &&
+        (2 * (size_t)d->n_spheres + 8) * 4 * 16 + mat_b + RTW_WF_CURSOR_BYTES(768u) <= RTW_WF_CLDS2_MAX)
+        orders = 4;
+    // (object scenes keep one ordering: their hit ids carry an instance member where sphere scenes carry the copy)
+    if (tu.bvh_orders) orders = (d->bvh_mode == RTW_BVH_SAH && !objects && tu.bvh_orders > 1) ? tu.bvh_orders : 1u;
+    return orders;
+}
+
+// The hit id is one 32-bit word, -1 = miss: leaf node | instance member << bits.  Without instance trees
+// the split is fixed (24 node bits, 7 member bits: lists of at most 127).  With them (RTW_F_TREE) it is
+// per scene: as many bits as the world tree's nodes need, the rest up to bit 30 for the member.
+int split_hit_id(const rtw_geometry& geom, size_t nodes, uint32_t* hit_bits) {
+    *hit_bits = RTW_HIT_NODE_BITS;
+    if (geom.feat & RTW_F_TREE) {
+        auto bits = [](uint64_t max_value) {
+            uint32_t b = 1;
+            while (b < 32 && (max_value >> b)) b++;
+            return b;
+        };
+        uint32_t max_count = 1;
+        for (const rtw_dev_instance& in : geom.insts) max_count = std::max(max_count, in.count);
+        const uint32_t nb = bits(nodes - 1), mb = bits(max_count - 1);
+        if (nb + mb > 31) {
+            char msg[200];
+            std::snprintf(msg, sizeof msg,
+                          "hit id limit: %zu BVH nodes (%u bits) and an instance of %u members (%u bits) need more "
+                          "than 31 bits together", nodes, nb, max_count, mb);
+            return fail(RTW_E_INVALID, msg);
+        }
+        *hit_bits = nb;
+    } else if ((geom.feat & RTW_F_GEOM) && nodes >= (1u << RTW_HIT_NODE_BITS)) {
+        return fail(RTW_E_INVALID, "scenes with instances are limited to 2^24 BVH nodes");
+    }
+    return RTW_OK;
+}
+
+// The walks' derived records of a GPU context's static sphere SAH tree (empty where they do not apply)
+struct WalkRecords {
+    std::vector<rtw_cnode> cnodes;  // compact 16-B walk (rtw_compact_nodes), or with cnode32 the 32-B fp32-box form
+    bool cnode32 = false;
+    std::vector<rtw_cnode> w2;      // two-wide records for the stack walk of trees read through L1/L2 (rtw_wide2_nodes)
+    std::vector<uint32_t> w2leaf;
+    uint32_t w2_stack = 0;
+};
+void build_walk_records(const rtw_scene_desc* d, const rtw_tuning& tu, const rtw_ctx* ctx, uint32_t orders,
+                        bool objects, WalkRecords& R) {
+    const std::vector<rtw_node>& nodes = ctx->nodes_host;
+    bool want = d->bvh_mode == RTW_BVH_SAH && !objects && ctx->box_pad > 0 && tu.compact_nodes &&
+                ctx->device != RTW_DEVICE_CPU;
+    for (uint32_t i = 0; want && i < d->n_spheres; i++) want = !d->spheres[i].is_moving;
+    // compact_nodes 2: the 32-B fp32-box form where it applies (4 copies), else the 16-B fp16 form
+    R.cnode32 = want && tu.compact_nodes == 2 && orders == 4 && rtw_compact_nodes(nodes, orders, R.cnodes, true);
+    if (want && !R.cnode32 && !rtw_compact_nodes(nodes, orders, R.cnodes)) R.cnodes.clear();
+    if (!R.cnodes.empty() && !R.cnode32 && tu.wide_walk && tu.sah_max_leaf <= 1 &&
+        !rtw_wide2_nodes(nodes, (uint32_t)(nodes.size() / orders), R.w2, R.w2leaf, &R.w2_stack))
+        R.w2.clear();
+    if (R.w2_stack > RTW_W2_STACK_MAX) R.w2.clear();
+}
+
+// The device records of the description's materials, textures (one more, zero), Perlin tables (one more) and
+// images (each 256-B aligned in `bytes`; one more info record)
+std::vector<rtw_dev_material> dev_materials(const rtw_scene_desc* d) {
+    std::vector<rtw_dev_material> out(d->n_materials);
+    for (uint32_t i = 0; i < d->n_materials; i++) {
+        rtw_dev_material& m = out[i];
+        m.kind = d->materials[i].kind;
+        m.texture = d->materials[i].texture;
+        m.fuzz = d->materials[i].fuzz;
+        m.ir = d->materials[i].ir;
+        for (int k = 0; k < 3; k++) m.albedo[k] = d->materials[i].albedo[k];
+    }
+    return out;
+}
+std::vector<rtw_dev_texture> dev_textures(const rtw_scene_desc* d) {
+    std::vector<rtw_dev_texture> out(d->n_textures + 1);
+    for (uint32_t i = 0; i < d->n_textures; i++) {
+        rtw_dev_texture& t = out[i];
+        const rtw_texture& s = d->textures[i];
+        t.kind = s.kind; t.image = s.image; t.perlin = s.perlin; t.scale = s.scale;
+        for (int k = 0; k < 3; k++) { t.even[k] = s.even[k]; t.odd[k] = s.odd[k]; }
+    }
+    return out;
+}
+std::vector<uint8_t> dev_perlins(const rtw_scene_desc* d) {
+    std::vector<uint8_t> out((size_t)(d->n_perlins + 1) * RTW_PERLIN_BYTES, 0);
+    for (uint32_t i = 0; i < d->n_perlins; i++) {
+        uint8_t* base = out.data() + (size_t)i * RTW_PERLIN_BYTES;
+        float* vec = reinterpret_cast<float*>(base);
+        for (int k = 0; k < 256; k++) {
+            vec[4 * k + 0] = d->perlins[i].ranvec[k][0];
+            vec[4 * k + 1] = d->perlins[i].ranvec[k][1];
+            vec[4 * k + 2] = d->perlins[i].ranvec[k][2];
+            vec[4 * k + 3] = 0.0f;
+        }
+        uint32_t* perm = reinterpret_cast<uint32_t*>(base + 256 * 16);
+        for (int k = 0; k < 256; k++) {
+            perm[k] = d->perlins[i].perm_x[k];
+            perm[256 + k] = d->perlins[i].perm_y[k];
+            perm[512 + k] = d->perlins[i].perm_z[k];
+        }
+    }
+    return out;
+}
+void dev_images(const rtw_scene_desc* d, std::vector<rtw_dev_image>& info, std::vector<uint8_t>& bytes) {
+    info.assign(d->n_images + 1, rtw_dev_image{});
+    size_t total = 0;
+    for (uint32_t i = 0; i < d->n_images; i++) {
+        info[i].offset = total;
+        info[i].width = d->images[i].width;
+        info[i].height = d->images[i].height;
+        info[i].bytes_per_row = d->images[i].bytes_per_row;
+        total += ((size_t)d->images[i].bytes_per_row * d->images[i].height + 255) & ~size_t(255);
+    }
+    bytes.assign(total, 0);
+    for (uint32_t i = 0; i < d->n_images; i++) {
+        const size_t nb = (size_t)d->images[i].bytes_per_row * d->images[i].height;
+        if (nb) std::memcpy(bytes.data() + info[i].offset, d->images[i].data, nb);
+    }
+}
+
+// Everything the scene blob is made of besides the world tree (ctx->nodes_host)
+struct SceneParts {
+    rtw_geometry geom;
+    WalkRecords walk;
+    std::vector<rtw_dev_material> mats;
+    std::vector<rtw_dev_texture> texs;
+    std::vector<rtw_dev_image> img_info;
+    std::vector<uint8_t> perlin, images;
+};
+
+// One section of the scene blob: `bytes` copied from src, `pad` more reserved behind them (zero), the sum rounded
+// up to 256 B; `present` false: the section's launch pointer is null (its bytes, if any, are laid out all the same)
+struct Section {
+    const void* src;
+    size_t bytes, pad;
+    bool present;
+    size_t off;
+};
+template <typename T>
+Section section(const std::vector<T>& v, size_t pad = 0, bool present = true) {
+    return Section{v.data(), v.size() * sizeof(T), pad, present, 0};
+}
+// Blob layout, in this order: nodes | cvec | spheres | quads | members | instances | media | materials | textures |
+// images-info | perlin | image bytes || compact nodes | two-wide records | their leaf ids | instance trees.
+// The scene image that rtw_scene_hash covers is [S_CVEC, S_CNOD): the walks' derived records behind it depend on
+// the backend and the tuning, so a checkpoint's hash matches on every context of the same scene (the node array,
+// whose layout also follows the tuning, is left out of the hash as well).
+enum { S_NODES, S_CVEC, S_SPH, S_QUAD, S_MEMB, S_INST, S_MED, S_MATS, S_TEXS, S_IMGI, S_PERL, S_IMGS, S_CNOD, S_W2,
+       S_W2L, S_INOD, S_COUNT };
+struct Blob {
+    Section s[S_COUNT];
+    size_t bytes;
+    template <typename T>
+    const T* at(const uint8_t* base, int k) const {
+        return s[k].present ? reinterpret_cast<const T*>(base + s[k].off) : nullptr;
+    }
+};
+Blob lay_out_blob(const rtw_ctx* ctx, const SceneParts& P) {
+    const rtw_geometry& g = P.geom;
+    const bool w2 = !P.walk.w2.empty();
+    Blob B{{section(ctx->nodes_host), section(g.cvec, 16), section(g.spheres, 16), section(g.quads, 16),
+            section(g.members, 16), section(g.insts, 16), section(g.media, 16), section(P.mats), section(P.texs),
+            section(P.img_info), section(P.perlin), section(P.images, 16),
+            section(P.walk.cnodes, 0, !P.walk.cnodes.empty()), section(P.walk.w2, 0, w2),
+            section(P.walk.w2leaf, 0, w2), section(g.inodes, 0, !g.inodes.empty())},
+           0};
+    for (Section& x : B.s) {
+        x.off = B.bytes;
+        B.bytes = (B.bytes + x.bytes + x.pad + 255) & ~size_t(255);
+    }
+    return B;
+}
+std::vector<uint8_t> fill_blob(const Blob& B) {
+    std::vector<uint8_t> blob(B.bytes, 0);
+    for (const Section& x : B.s)
+        if (x.bytes) std::memcpy(blob.data() + x.off, x.src, x.bytes);
+    return blob;
+}
+
+// FNV-1a 64 of the scene image (rtw_scene_hash): the tree kind (and the reference topology's seed),
+// then every section after the nodes -- the node array's layout depends on the tuning (orderings,
+// hoisting, object_tree), the image does not
+uint64_t hash_blob(const rtw_scene_desc* d, const std::vector<uint8_t>& blob, const Blob& B) {
+    uint64_t h = 0xCBF29CE484222325ull;
+    const uint64_t key[2] = {(uint64_t)d->bvh_mode, d->bvh_mode == RTW_BVH_REFERENCE ? (uint64_t)d->bvh_seed : 0ull};
+    const unsigned char* kb = reinterpret_cast<const unsigned char*>(key);
+    for (size_t i = 0; i < sizeof key; i++) h = (h ^ kb[i]) * 0x100000001B3ull;
+    for (size_t i = B.s[S_CVEC].off; i < B.s[S_CNOD].off; i++) h = (h ^ blob[i]) * 0x100000001B3ull;
+    return h;
+}
+
+int upload_blob(rtw_ctx* ctx, const std::vector<uint8_t>& blob) {
+    hipError_t e = hipSetDevice(ctx->device);
+    // blocking stream: orders with the legacy NULL stream (torch's default), so a caller passing
+    // device buffers and stream == NULL sees its prior NULL-stream work (e.g. zero fills) complete first
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamDefault);
+    if (e == hipSuccess) e = hipMalloc(&ctx->d_blob, blob.size());
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&ctx->d_dbg, 64 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&ctx->d_work, 256);
+    return e == hipSuccess ? RTW_OK : hip_fail(e, "rtw_scene_create upload");
+}
+
+// the launch's scene pointers: the sections of the blob at `base` (the device copy, or a host context's own)
+void set_scene_pointers(rtw_launch& L, const uint8_t* base, const Blob& B, const WalkRecords& walk) {
+    L.nodes = B.at<float4>(base, S_NODES);
+    L.cvec = B.at<float4>(base, S_CVEC);
+    L.sph = B.at<rtw_dev_sphere>(base, S_SPH);
+    L.quads = B.at<rtw_dev_quad>(base, S_QUAD);
+    L.members = B.at<uint32_t>(base, S_MEMB);
+    L.insts = B.at<rtw_dev_instance>(base, S_INST);
+    L.media = B.at<rtw_dev_medium>(base, S_MED);
+    L.mats = B.at<rtw_dev_material>(base, S_MATS);
+    L.texs = B.at<rtw_dev_texture>(base, S_TEXS);
+    L.img_info = B.at<rtw_dev_image>(base, S_IMGI);
+    L.perlin = B.at<float4>(base, S_PERL);
+    L.images = B.at<uint8_t>(base, S_IMGS);
+    L.cnodes = B.at<uint4>(base, S_CNOD);
+    L.w2nodes = B.at<uint4>(base, S_W2);
+    L.w2leaf = B.at<uint32_t>(base, S_W2L);
+    L.w2_stack = walk.w2.empty() ? 0u : walk.w2_stack;
+    L.inodes = B.at<float4>(base, S_INOD);
+    L.cnode32 = walk.cnode32 ? 1u : 0u;
+    L.n_lights = 0;  // rtw_scene_set_lights
+    L.lights = nullptr;
+    L.vattrs = nullptr;  // rtw_scene_set_vertex_attrs
+}
+
+// the host copies the context keeps: what rtw_scene_set_lights / rtw_scene_set_vertex_attrs validate against and
+// what rtw_scene_instance_nodes gives back
+void keep_host_copies(rtw_ctx* ctx, const rtw_scene_desc* d, const rtw_geometry& geom) {
+    ctx->quads_host = geom.quads;
+    ctx->spheres_host = geom.spheres;
+    ctx->members_host = geom.members;
+    for (const rtw_dev_medium& m : geom.media) ctx->boundaries_host.push_back(m.boundary);
+    for (uint32_t i = 0; i < d->n_materials; i++) ctx->mat_kind_host.push_back(d->materials[i].kind);
+    ctx->inodes_host = geom.inodes;
+    ctx->inst_tree.clear();
+    for (const rtw_dev_instance& in : geom.insts)
+        ctx->inst_tree.emplace_back(in.tree ? in.tree - 1u : 0u, in.tree ? 2u * in.count - 1u : 0u);
+}
+
+void set_stats(rtw_ctx* ctx, const rtw_scene_desc* d, uint32_t orders, uint32_t depth, uint32_t draws,
+               uint32_t n_hoisted) {
+    rtw_scene_stats& st = ctx->stats;
+    st.n_nodes = (uint32_t)(ctx->nodes_host.size() / orders);  // per ordering
+    st.n_leaves = d->objects ? d->n_objects : d->n_spheres;
+    st.n_inner = st.n_nodes - st.n_leaves;
+    st.depth = depth;
+    st.device_bytes = ctx->blob_bytes;
+    st.axis_draws = draws;
+    st.n_hoisted = n_hoisted;
+    st.extent = ctx->extent;
+    st.box_pad = ctx->box_pad;
+}
+
+// the wavefront's batch and iteration knobs, and the device's size
+void set_wavefront_knobs(rtw_ctx* ctx, const rtw_tuning& tu, uint32_t sfeat) {
+    const bool host = ctx->device == RTW_DEVICE_CPU;
+    ctx->wf_deal = tu.deal;
+    {
+        // wavefront batch capacity: up to 2^29 paths (BASELINE config 2 = 480M samples in one
+        // batch: one drain of long paths per render instead of one per 64M), within ~35 % of
+        // the device's FREE memory at scene creation (RTW_WF_PATH_BYTES per path); the
+        // allocation halves the batch on failure (run_wavefront)
+        size_t free_b = 0, total_b = 0;
+        uint64_t cap = 1ull << 29;
+        if (!host && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b)
+            cap = std::min<uint64_t>(cap, (uint64_t)(0.35 * (double)free_b) / RTW_WF_PATH_BYTES);
+        ctx->wf_max_paths = tu.wf_paths ? tu.wf_paths : std::max<uint64_t>(cap, 1u << 20);
+    }
+    // Round 5, with the dynamic tail (deal bit 2): fewer iterations before the tail pay everywhere but on
+    // image-textured scenes -- same-box A/B, 9 -> 4 iterations: C2 +3.7 %, C4 +3.3 %, Cornell +6.8 %, smoke
+    // +1.2 %, simple_light +1.9 %.  Image-textured scenes run no tail at all (every bounce a wavefront
+    // iteration: the launcher clamps to max_depth): C5 9 / 24 / 32 / 50 iterations 9425 / 9750 / 9816 / 9990
+    // Msamples/s (profiles/r5_iters/).
+    ctx->wf_iters = tu.wf_iters ? tu.wf_iters : (sfeat & RTW_F_IMAGE) ? (uint32_t)RTW_WF_MAX_ITERS : 4u;
+    ctx->wf_sort_iters = tu.sort_iters;
+    ctx->wf_sort_iters_split = tu.sort_iters_split;
+    ctx->wf_sort_mask = (1u << tu.sort_bits) - 1u;
+    int n_cu = 0;
+    if (host || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess ||
+        n_cu < 1)
+        n_cu = 256;
+    ctx->n_cu = n_cu;
+    ctx->cpu_threads = tu.cpu_threads;
+}
+
+// the launch's knobs (ctx->base): what the tuning and the built scene make of the kernels' switches
+void set_launch_knobs(rtw_ctx* ctx, const rtw_scene_desc* d, const rtw_tuning& tu, uint32_t orders, const Blob& B) {
+    rtw_launch& L = ctx->base;
+    const uint32_t n_nodes = ctx->stats.n_nodes;  // per ordering
+    // default cap: 32 candidates for small trees (flat prepass: C2 16/32/64 -> 5765/5789/5769), 128 for large
+    // ones (frustum-walked prepass: C4 32/64 -> 2440/2458; round 6, 64/96/128 -> 3147/3156/3166,
+    // profiles/r6_late_rest/)
+    L.tile_lists = tu.tile_lists == 1 ? (n_nodes <= 4096 ? 32u : 128u) : std::min<uint32_t>(tu.tile_lists, RTW_TL_MAX);
+    L.n_nodes = n_nodes;
+    L.n_orders = orders;
+    L.clds_shape = tu.clds_shape ? tu.clds_shape : 4u;  // auto: two 768-thread blocks where the stage fits
+    L.n_perlin = d->n_perlins;
+    L.feat = ctx->feat;
+    L.work_counter = ctx->d_work;
+    L.shade_min = tu.mega_shade_min;
+    L.waves = tu.mega_waves;
+    L.tile_order = tu.mega_tile_order ? 1u : 0u;
+    // (an unfiltered variant measured +-0 on C2 and -20 % on C4: its codegen slowed the L1/L2 walk)
+    L.fast_reject = tu.fast_reject ? 1u : 0u;
+    // the octant copies do not fit the megakernel's stage
+    L.use_lds = orders == 1 && (tu.lds & RTW_LDS_MEGA_NODES) ? 1u : 0u;
+    // wavefront trace: node array staged in LDS when one ordering fits (object scenes,
+    // reference trees; +2 % on Cornell); the 8 octant copies of SAH sphere trees do not
+    L.wf_lds = (tu.lds & RTW_LDS_NODES) ? 1u : 0u;
+    // small static sphere SAH trees: the compact nodes of all 8 orders in LDS (C2: +1 %)
+    L.wf_clds = (tu.lds & RTW_LDS_CNODES) ? 1u : 0u;
+    // compact LDS stage: gen, trace and shade of an iteration fused in one kernel
+    // (the ray/hit hand-off through HBM disappears), tail on the LDS stage
+    L.wf_fuse = tu.fuse & 7u;
+    // Perlin tables (7 KiB each) staged in LDS by the fused step when at most 4 (noise scenes)
+    L.perlin_lds = (ctx->feat & RTW_F_NOISE) && d->n_perlins <= 4 && (tu.lds & RTW_LDS_PERLIN) ? 1u : 0u;
+    // materials of sphere scenes staged in LDS by the compact-LDS fused step when they fit beside the
+    // nodes (wf_run_fused checks the total): hit_prep's material load stops waiting on L1/L2
+    const size_t mat_bytes = (d->n_materials * sizeof(rtw_dev_material) + 15) & ~size_t(15);
+    L.mat_lds = (tu.lds & RTW_LDS_MATERIALS) ? (uint32_t)mat_bytes : 0u;
+    const size_t shade_bytes = B.s[S_PERL].off - B.s[S_MATS].off;
+    L.shade_lds = shade_bytes <= 8192 && (tu.lds & RTW_LDS_SHADE) ? (uint32_t)shade_bytes : 0u;
+    // quads, instance member lists and instances of small object scenes (Cornell: ~2 KiB) staged in LDS
+    // with the node array: the member loop's loads stop waiting on L1
+    const size_t geom_bytes = B.s[S_MED].off - B.s[S_QUAD].off;
+    const bool geom_fits = (ctx->feat & RTW_F_GEOM) && geom_bytes <= 16384;
+    L.geom_lds = geom_fits && (tu.lds & RTW_LDS_GEOMETRY) ? (uint32_t)geom_bytes : 0u;
+    // SAH trees: FMA slab test on the padded boxes (only enlarges the set of visited nodes;
+    // reference trees keep the exact aabb.zig walk)
+    L.fast_box = ctx->box_pad > 0 && tu.fast_box ? 1u : 0u;
+    L.inst_cull = (tu.object_tree & RTW_OTREE_NO_CULL) ? 0u : 1u;  // consulted only with fast_box
+    if (ctx->device == RTW_DEVICE_CPU) {  // the exact aabb.zig slab test and IEEE sphere test (the hardware
+        L.fast_box = 0;                   // estimates are device-only)
+        L.fast_reject = 0;
+    }
+}
+
+struct CtxDestroy {
+    void operator()(rtw_ctx* ctx) const { rtw_scene_destroy(ctx); }
+};
+
+// The upload-and-publish step of a registration (rtw_scene_set_lights, rtw_scene_set_vertex_attrs; the caller
+// holds ctx->mu): the records `rec` become the context's -- `kept` on the host and, on a GPU context, *d_buf,
+// allocated for `cap` records at the first registration -- and `ptr`, the field of `base` the kernels read them
+// through, addresses them (null: none registered).
+template <typename T>
+int publish_records(rtw_ctx* ctx, rtw_launch& base, std::vector<T>& kept, const std::vector<T>& rec, T** d_buf,
+                    size_t cap, const T*& ptr) {
+    const bool host = ctx->device == RTW_DEVICE_CPU;
+    if (!host) {
+        HIP_TRY(hipSetDevice(ctx->device));
+        // a render left on a caller's stream (RTW_RENDER_NO_SYNC) may still read the records
+        if (ctx->last_done) HIP_TRY(hipEventSynchronize(ctx->last_done));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (!rec.empty() && !*d_buf) HIP_TRY(hipMalloc(reinterpret_cast<void**>(d_buf), cap * sizeof(T)));
+        if (!rec.empty()) HIP_TRY(hipMemcpy(*d_buf, rec.data(), rec.size() * sizeof(T), hipMemcpyHostToDevice));
+    }
+    kept = rec;
+    ptr = rec.empty() ? nullptr : host ? kept.data() : *d_buf;
+    // the persistent kernel's resident grid is its instantiation's
+    if (!host) ctx->grid = rtw_persistent_grid(rtw_feat_of(base), ctx->stats.n_nodes, base.use_lds != 0);
+    return RTW_OK;
 }
 }  // namespace
 
@@ -176,50 +619,9 @@ int rtw_scene_create_ex(const rtw_scene_desc* d, int device, const rtw_tuning* t
     rtw_tuning tu;
     rtw_tuning_defaults(&tu);
     if (tuning) tu = *tuning;
-    if (tu.kernel > RTW_KERNEL_SIMPLE) return fail(RTW_E_INVALID, "tuning.kernel out of range");
-    if (tu.bvh_orders != 0 && tu.bvh_orders != 1 && tu.bvh_orders != 4 && tu.bvh_orders != 8)
-        return fail(RTW_E_INVALID, "tuning.bvh_orders must be 0, 1, 4 or 8");
-    if (tu.clds_shape != 0 && tu.clds_shape != 1 && tu.clds_shape != 4)
-        return fail(RTW_E_INVALID, "tuning.clds_shape must be 0, 1 or 4 (ABI 8)");
-    if (tu.deal & ~(uint32_t)RTW_DEAL_ALL)
-        return fail(RTW_E_INVALID, "tuning.deal: bits 1 | 2 | 8 | 16 | 32 | 128 (RTW_DEAL_*)");
-    if (tu.wf_iters > RTW_WF_MAX_ITERS) return fail(RTW_E_INVALID, "tuning.wf_iters out of range");
-    if ((tu.object_tree & 0xFFu) > 100 || (tu.object_tree & ~(0xFFu | RTW_OTREE_NO_CULL)))
-        return fail(RTW_E_INVALID, "tuning.object_tree: 0..100 [| RTW_OTREE_NO_CULL]");
-    if (tu.sort_bits > RTW_WF_BUCKET_BITS) return fail(RTW_E_INVALID, "tuning.sort_bits out of range");
-    if (tu.mega_shade_min < 1 || tu.mega_shade_min > 64) return fail(RTW_E_INVALID, "tuning.mega_shade_min out of range");
-    if (tu.mega_waves != 1 && tu.mega_waves != 6 && tu.mega_waves != 8) return fail(RTW_E_INVALID, "tuning.mega_waves must be 1, 6 or 8");
-    if (tu.wf_paths && tu.wf_paths < 4096) return fail(RTW_E_INVALID, "tuning.wf_paths must be 0 or >= 4096");
+    if (int rc = check_tuning(tu)) return rc;
     *out = nullptr;
-    if ((d->n_spheres && !d->spheres) || (d->objects ? d->n_objects : d->n_spheres) == 0)
-        return fail(RTW_E_INVALID, "scene has no objects");
-    if (d->n_materials == 0 || !d->materials) return fail(RTW_E_INVALID, "scene has no materials");
-    for (uint32_t i = 0; i < d->n_spheres; i++)
-        if (d->spheres[i].material >= d->n_materials) return fail(RTW_E_INVALID, "sphere material index out of range");
-    for (uint32_t i = 0; i < d->n_materials; i++) {
-        const rtw_material& m = d->materials[i];
-        if (m.kind > RTW_MAT_ISOTROPIC) return fail(RTW_E_INVALID, "unknown material kind");
-        const bool textured = m.kind == RTW_MAT_LAMBERTIAN || m.kind == RTW_MAT_DIFFUSE_LIGHT || m.kind == RTW_MAT_ISOTROPIC;
-        if (textured && m.texture >= d->n_textures) return fail(RTW_E_INVALID, "material texture index out of range");
-    }
-    for (uint32_t i = 0; i < d->n_textures; i++) {
-        const rtw_texture& t = d->textures[i];
-        if (t.kind > RTW_TEX_NOISE) return fail(RTW_E_INVALID, "unknown texture kind");
-        if (t.kind == RTW_TEX_IMAGE && t.image >= d->n_images) return fail(RTW_E_INVALID, "texture image index out of range");
-        if (t.kind == RTW_TEX_NOISE && t.perlin >= d->n_perlins) return fail(RTW_E_INVALID, "texture perlin index out of range");
-    }
-    for (uint32_t i = 0; d->quads && i < d->n_quads; i++)
-        if (d->quads[i].shape > RTW_QUAD_TRIANGLE) {
-            char msg[160];
-            std::snprintf(msg, sizeof msg, "quad %u: unknown shape %u (RTW_QUAD_PARALLELOGRAM = 0 or RTW_QUAD_TRIANGLE = 1)",
-                          i, d->quads[i].shape);
-            return fail(RTW_E_INVALID, msg);
-        }
-    for (uint32_t i = 0; i < d->n_images; i++) {
-        const rtw_image& im = d->images[i];
-        if (im.width && im.height && (!im.data || im.bytes_per_row < 4 * im.width))
-            return fail(RTW_E_INVALID, "bad image");
-    }
+    if (int rc = check_desc(d)) return rc;
     const bool host = device == RTW_DEVICE_CPU;  // a host context: no GPU involved (rtw_cpu.hip)
     if (!host) {
         int ndev = 0;
@@ -227,315 +629,40 @@ int rtw_scene_create_ex(const rtw_scene_desc* d, int device, const rtw_tuning* t
         if (device < 0 || device >= ndev) return fail(RTW_E_INVALID, "device index out of range");
     }
 
-    rtw_ctx* ctx = new rtw_ctx();
+    std::unique_ptr<rtw_ctx, CtxDestroy> ctx(new rtw_ctx());
     ctx->device = device;
-    rtw_geometry geom;
-    uint32_t depth = 0, draws = 0;
-    // SAH trees of sphere scenes: 8 octant-ordered copies of the node array (tuning.bvh_orders 4: copies by the
-    // x and z signs; 1: one, ordered
-    // along order_dir).  Scenes with quads/instances/media keep one order: their leaf tests are costly, and
-    // lanes walking different orders stop executing them together (Cornell: -31 % with 8 orders).
+    SceneParts P;
     const bool objects = d->n_quads || d->n_instances || d->n_media;
-    uint32_t orders = (d->bvh_mode == RTW_BVH_SAH && !objects) ? 8u : 1u;
-    // Round 5: small static untextured sphere trees (Book-1, C2 / C3) take 4 copies (x, z signs): their compact
-    // stage (+ materials) then fits half the LDS and the fused step and tail run two 768-thread blocks per CU, 6
-    // waves per SIMD (C2 +4.6 %, profiles/r5_stage/).  (A tree of ~2 nodes per sphere; the check is redone on the
-    // built tree by the launcher, which falls back to one block.)
     const uint32_t sfeat = scene_features(d);
-    const size_t mat_b = (size_t)d->n_materials * sizeof(rtw_dev_material);
-    if (orders == 8 && !tu.bvh_orders && tu.compact_nodes == 1 && tu.fast_box && !(sfeat & ~RTW_F_CHECKER) &&
-        (2 * (size_t)d->n_spheres + 8) * 4 * 16 + mat_b + RTW_WF_CURSOR_BYTES(768u) <= RTW_WF_CLDS2_MAX)
-        orders = 4;
-    // (object scenes keep one ordering: their hit ids carry an instance member where sphere scenes carry the copy)
-    if (tu.bvh_orders) orders = (d->bvh_mode == RTW_BVH_SAH && !objects && tu.bvh_orders > 1) ? tu.bvh_orders : 1u;
-    uint32_t n_hoisted = 0;
-    int rc = rtw_build_bvh(*d, ctx->nodes_host, geom, &depth, &draws, &ctx->box_pad, &ctx->extent, orders,
-                           tu.sah_max_leaf, tu.hoist && !objects ? 1u : 0u, &n_hoisted, objects ? (tu.object_tree & 0xFFu) : 0u);
-    if (rc != RTW_OK) {
-        delete ctx;
-        return fail(rc, "BVH build failed (bad object graph or bvh_mode)");
-    }
-    // The hit id is one 32-bit word, -1 = miss: leaf node | instance member << bits.  Without instance trees
-    // the split is fixed (24 node bits, 7 member bits: lists of at most 127).  With them (RTW_F_TREE) it is
-    // per scene: as many bits as the world tree's nodes need, the rest up to bit 30 for the member.
-    uint32_t hit_bits = RTW_HIT_NODE_BITS;
-    if (geom.feat & RTW_F_TREE) {
-        auto bits = [](uint64_t max_value) {
-            uint32_t b = 1;
-            while (b < 32 && (max_value >> b)) b++;
-            return b;
-        };
-        uint32_t max_count = 1;
-        for (const rtw_dev_instance& in : geom.insts) max_count = std::max(max_count, in.count);
-        const uint32_t nb = bits(ctx->nodes_host.size() - 1), mb = bits(max_count - 1);
-        if (nb + mb > 31) {
-            char msg[200];
-            std::snprintf(msg, sizeof msg,
-                          "hit id limit: %zu BVH nodes (%u bits) and an instance of %u members (%u bits) need more "
-                          "than 31 bits together", ctx->nodes_host.size(), nb, max_count, mb);
-            delete ctx;
-            return fail(RTW_E_INVALID, msg);
-        }
-        hit_bits = nb;
-    } else if ((geom.feat & RTW_F_GEOM) && ctx->nodes_host.size() >= (1u << RTW_HIT_NODE_BITS)) {
-        delete ctx;
-        return fail(RTW_E_INVALID, "scenes with instances are limited to 2^24 BVH nodes");
-    }
-    const std::vector<float>& cvec = geom.cvec;
-    // compact 16-B walk for static sphere SAH trees (rtw_compact_nodes)
-    std::vector<rtw_cnode> cnodes;
-    bool cnode32 = false;
-    {
-        bool want = d->bvh_mode == RTW_BVH_SAH && !objects && ctx->box_pad > 0 && tu.compact_nodes && !host;
-        for (uint32_t i = 0; want && i < d->n_spheres; i++) want = !d->spheres[i].is_moving;
-        // compact_nodes 2: the 32-B fp32-box form where it applies (4 copies), else the 16-B fp16 form
-        cnode32 = want && tu.compact_nodes == 2 && orders == 4 && rtw_compact_nodes(ctx->nodes_host, orders, cnodes, true);
-        if (want && !cnode32 && !rtw_compact_nodes(ctx->nodes_host, orders, cnodes)) cnodes.clear();
-    }
-    // two-wide records for the stack walk of trees read through L1/L2 (rtw_wide2_nodes)
-    std::vector<rtw_cnode> w2;
-    std::vector<uint32_t> w2leaf;
-    uint32_t w2_stack = 0;
-    if (!cnodes.empty() && !cnode32 && tu.wide_walk && tu.sah_max_leaf <= 1 &&
-        !rtw_wide2_nodes(ctx->nodes_host, (uint32_t)(ctx->nodes_host.size() / orders), w2, w2leaf, &w2_stack))
-        w2.clear();
-    if (w2_stack > RTW_W2_STACK_MAX) w2.clear();
-
-    // Blob layout (each section 256-B aligned): nodes | cvec | spheres | quads | members | instances | media |
-    // materials | textures | images-info | perlin | image bytes || compact nodes | two-wide records (not hashed)
-    auto align = [](size_t x) { return (x + 255) & ~size_t(255); };
-    const size_t n_nodes = ctx->nodes_host.size() / orders;  // per ordering
-    size_t off = 0;
-    const size_t o_nodes = off; off = align(off + ctx->nodes_host.size() * sizeof(rtw_node));
-    const size_t o_cvec = off; off = align(off + cvec.size() * sizeof(float) + 16);
-    const size_t o_sph = off; off = align(off + geom.spheres.size() * sizeof(rtw_dev_sphere) + 16);
-    const size_t o_quad = off; off = align(off + geom.quads.size() * sizeof(rtw_dev_quad) + 16);
-    const size_t o_memb = off; off = align(off + geom.members.size() * sizeof(uint32_t) + 16);
-    const size_t o_inst = off; off = align(off + geom.insts.size() * sizeof(rtw_dev_instance) + 16);
-    const size_t o_med = off; off = align(off + geom.media.size() * sizeof(rtw_dev_medium) + 16);
-    const size_t o_mats = off; off = align(off + d->n_materials * sizeof(rtw_dev_material));
-    const size_t o_texs = off; off = align(off + (d->n_textures + 1) * sizeof(rtw_dev_texture));
-    const size_t o_imgi = off; off = align(off + (d->n_images + 1) * sizeof(rtw_dev_image));
-    const size_t o_perl = off; off = align(off + (size_t)(d->n_perlins + 1) * RTW_PERLIN_BYTES);
-    const size_t o_imgs = off;
-    std::vector<rtw_dev_image> img_info(d->n_images + 1);
-    size_t img_bytes = 0;
-    for (uint32_t i = 0; i < d->n_images; i++) {
-        img_info[i].offset = img_bytes;
-        img_info[i].width = d->images[i].width;
-        img_info[i].height = d->images[i].height;
-        img_info[i].bytes_per_row = d->images[i].bytes_per_row;
-        img_bytes += align((size_t)d->images[i].bytes_per_row * d->images[i].height);
-    }
-    off = align(off + img_bytes + 16);
-    // the scene image: the walks' derived records below (compact nodes, two-wide records) depend on the
-    // backend and the tuning, so a checkpoint's hash matches on every context of the same scene (the
-    // node array, whose layout also follows the tuning, is left out of the hash as well)
-    const size_t hashed = off;
-    const size_t o_cnod = off; off = align(off + cnodes.size() * sizeof(rtw_cnode));
-    const size_t o_w2 = off; off = align(off + w2.size() * sizeof(rtw_cnode));
-    const size_t o_w2l = off; off = align(off + w2leaf.size() * sizeof(uint32_t));
-    const size_t o_inod = off; off = align(off + geom.inodes.size() * sizeof(rtw_node));  // the instance trees
-
-    std::vector<uint8_t> blob(off, 0);
-    std::memcpy(blob.data() + o_nodes, ctx->nodes_host.data(), ctx->nodes_host.size() * sizeof(rtw_node));
-    auto put = [&](size_t o, const void* src, size_t nb) {
-        if (nb) std::memcpy(blob.data() + o, src, nb);
-    };
-    put(o_cnod, cnodes.data(), cnodes.size() * sizeof(rtw_cnode));
-    put(o_w2, w2.data(), w2.size() * sizeof(rtw_cnode));
-    put(o_w2l, w2leaf.data(), w2leaf.size() * sizeof(uint32_t));
-    put(o_inod, geom.inodes.data(), geom.inodes.size() * sizeof(rtw_node));
-    put(o_cvec, cvec.data(), cvec.size() * sizeof(float));
-    put(o_sph, geom.spheres.data(), geom.spheres.size() * sizeof(rtw_dev_sphere));
-    put(o_quad, geom.quads.data(), geom.quads.size() * sizeof(rtw_dev_quad));
-    put(o_memb, geom.members.data(), geom.members.size() * sizeof(uint32_t));
-    put(o_inst, geom.insts.data(), geom.insts.size() * sizeof(rtw_dev_instance));
-    put(o_med, geom.media.data(), geom.media.size() * sizeof(rtw_dev_medium));
-    for (uint32_t i = 0; i < d->n_materials; i++) {
-        rtw_dev_material m{};
-        m.kind = d->materials[i].kind;
-        m.texture = d->materials[i].texture;
-        m.fuzz = d->materials[i].fuzz;
-        m.ir = d->materials[i].ir;
-        for (int k = 0; k < 3; k++) m.albedo[k] = d->materials[i].albedo[k];
-        std::memcpy(blob.data() + o_mats + i * sizeof m, &m, sizeof m);
-    }
-    for (uint32_t i = 0; i < d->n_textures; i++) {
-        rtw_dev_texture t{};
-        const rtw_texture& s = d->textures[i];
-        t.kind = s.kind; t.image = s.image; t.perlin = s.perlin; t.scale = s.scale;
-        for (int k = 0; k < 3; k++) { t.even[k] = s.even[k]; t.odd[k] = s.odd[k]; }
-        std::memcpy(blob.data() + o_texs + i * sizeof t, &t, sizeof t);
-    }
-    std::memcpy(blob.data() + o_imgi, img_info.data(), img_info.size() * sizeof(rtw_dev_image));
-    for (uint32_t i = 0; i < d->n_perlins; i++) {
-        uint8_t* base = blob.data() + o_perl + (size_t)i * RTW_PERLIN_BYTES;
-        float* vec = reinterpret_cast<float*>(base);
-        for (int k = 0; k < 256; k++) {
-            vec[4 * k + 0] = d->perlins[i].ranvec[k][0];
-            vec[4 * k + 1] = d->perlins[i].ranvec[k][1];
-            vec[4 * k + 2] = d->perlins[i].ranvec[k][2];
-            vec[4 * k + 3] = 0.0f;
-        }
-        uint32_t* perm = reinterpret_cast<uint32_t*>(base + 256 * 16);
-        for (int k = 0; k < 256; k++) {
-            perm[k] = d->perlins[i].perm_x[k];
-            perm[256 + k] = d->perlins[i].perm_y[k];
-            perm[512 + k] = d->perlins[i].perm_z[k];
-        }
-    }
-    for (uint32_t i = 0; i < d->n_images; i++) {
-        const size_t nb = (size_t)d->images[i].bytes_per_row * d->images[i].height;
-        if (nb) std::memcpy(blob.data() + o_imgs + img_info[i].offset, d->images[i].data, nb);
-    }
-
-    if (!host) {
-        hipError_t e = hipSetDevice(device);
-        // blocking stream: orders with the legacy NULL stream (torch's default), so a caller passing
-        // device buffers and stream == NULL sees its prior NULL-stream work (e.g. zero fills) complete first
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamDefault);
-        if (e == hipSuccess) e = hipMalloc(&ctx->d_blob, off);
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_blob, blob.data(), off, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&ctx->d_dbg, 64 * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&ctx->d_work, 256);
-        if (e != hipSuccess) {
-            int code = hip_fail(e, "rtw_scene_create upload");
-            rtw_scene_destroy(ctx);
-            return code;
-        }
-    }
-    ctx->blob_bytes = off;
-    {   // FNV-1a 64 of the scene image (rtw_scene_hash): the tree kind (and the reference topology's seed),
-        // then every section after the nodes -- the node array's layout depends on the tuning (orderings,
-        // hoisting, object_tree), the image does not
-        uint64_t h = 0xCBF29CE484222325ull;
-        const uint64_t key[2] = {(uint64_t)d->bvh_mode, d->bvh_mode == RTW_BVH_REFERENCE ? (uint64_t)d->bvh_seed : 0ull};
-        const unsigned char* kb = reinterpret_cast<const unsigned char*>(key);
-        for (size_t i = 0; i < sizeof key; i++) h = (h ^ kb[i]) * 0x100000001B3ull;
-        for (size_t i = o_cvec; i < hashed; i++) h = (h ^ blob[i]) * 0x100000001B3ull;
-        ctx->scene_hash = h;
-    }
-    if (host) ctx->host_blob = blob;  // the launch pointers address the host copy
-    uint8_t* dev = host ? ctx->host_blob.data() : static_cast<uint8_t*>(ctx->d_blob);
-    rtw_launch& L = ctx->base;
-    L.nodes = reinterpret_cast<const float4*>(dev + o_nodes);
-    L.cnodes = cnodes.empty() ? nullptr : reinterpret_cast<const uint4*>(dev + o_cnod);
-    L.w2nodes = w2.empty() ? nullptr : reinterpret_cast<const uint4*>(dev + o_w2);
-    L.w2leaf = w2.empty() ? nullptr : reinterpret_cast<const uint32_t*>(dev + o_w2l);
-    L.w2_stack = w2.empty() ? 0u : w2_stack;
-    L.inodes = geom.inodes.empty() ? nullptr : reinterpret_cast<const float4*>(dev + o_inod);
-    L.hit_bits = hit_bits;
-    L.n_lights = 0;  // rtw_scene_set_lights
-    L.lights = nullptr;
-    L.vattrs = nullptr;  // rtw_scene_set_vertex_attrs
-    ctx->quads_host = geom.quads;  // what rtw_scene_set_lights validates a light against
-    ctx->spheres_host = geom.spheres;
-    ctx->members_host = geom.members;
-    for (const rtw_dev_medium& m : geom.media) ctx->boundaries_host.push_back(m.boundary);
-    for (uint32_t i = 0; i < d->n_materials; i++) ctx->mat_kind_host.push_back(d->materials[i].kind);
-    ctx->inodes_host = geom.inodes;
-    ctx->inst_tree.clear();
-    for (const rtw_dev_instance& in : geom.insts)
-        ctx->inst_tree.emplace_back(in.tree ? in.tree - 1u : 0u, in.tree ? 2u * in.count - 1u : 0u);
-    // default cap: 32 candidates for small trees (flat prepass: C2 16/32/64 -> 5765/5789/5769), 128 for large
-    // ones (frustum-walked prepass: C4 32/64 -> 2440/2458; round 6, 64/96/128 -> 3147/3156/3166,
-    // profiles/r6_late_rest/)
-    L.tile_lists = tu.tile_lists == 1 ? (n_nodes <= 4096 ? 32u : 128u) : std::min<uint32_t>(tu.tile_lists, RTW_TL_MAX);
-    L.cvec = reinterpret_cast<const float4*>(dev + o_cvec);
-    L.sph = reinterpret_cast<const rtw_dev_sphere*>(dev + o_sph);
-    L.quads = reinterpret_cast<const rtw_dev_quad*>(dev + o_quad);
-    L.members = reinterpret_cast<const uint32_t*>(dev + o_memb);
-    L.insts = reinterpret_cast<const rtw_dev_instance*>(dev + o_inst);
-    L.media = reinterpret_cast<const rtw_dev_medium*>(dev + o_med);
-    L.mats = reinterpret_cast<const rtw_dev_material*>(dev + o_mats);
-    L.texs = reinterpret_cast<const rtw_dev_texture*>(dev + o_texs);
-    L.img_info = reinterpret_cast<const rtw_dev_image*>(dev + o_imgi);
-    L.perlin = reinterpret_cast<const float4*>(dev + o_perl);
-    L.images = dev + o_imgs;
-    L.n_nodes = (uint32_t)n_nodes;
-    L.n_orders = orders;
-    L.clds_shape = tu.clds_shape ? tu.clds_shape : 4u;  // auto: two 768-thread blocks where the stage fits
-    ctx->wf_deal = tu.deal;
-    L.cnode32 = cnode32 ? 1u : 0u;
-    L.n_perlin = d->n_perlins;
-    ctx->feat = scene_features(d) | geom.feat;
-    L.feat = ctx->feat;
-    L.work_counter = ctx->d_work;
+    const uint32_t orders = choose_orders(d, tu, sfeat, objects);
+    uint32_t depth = 0, draws = 0, n_hoisted = 0;
+    int rc = rtw_build_bvh(*d, ctx->nodes_host, P.geom, &depth, &draws, &ctx->box_pad, &ctx->extent, orders,
+                           tu.sah_max_leaf, tu.hoist && !objects ? 1u : 0u, &n_hoisted,
+                           objects ? (tu.object_tree & 0xFFu) : 0u);
+    if (rc != RTW_OK) return fail(rc, "BVH build failed (bad object graph or bvh_mode)");
+    if (int rh = split_hit_id(P.geom, ctx->nodes_host.size(), &ctx->base.hit_bits)) return rh;
+    build_walk_records(d, tu, ctx.get(), orders, objects, P.walk);
+    P.mats = dev_materials(d);
+    P.texs = dev_textures(d);
+    P.perlin = dev_perlins(d);
+    dev_images(d, P.img_info, P.images);
+    const Blob B = lay_out_blob(ctx.get(), P);
+    std::vector<uint8_t> blob = fill_blob(B);
+    if (!host)
+        if (int ru = upload_blob(ctx.get(), blob)) return ru;
+    ctx->blob_bytes = B.bytes;
+    ctx->scene_hash = hash_blob(d, blob, B);
+    if (host) ctx->host_blob = std::move(blob);  // the launch pointers address the host copy
+    set_scene_pointers(ctx->base, host ? ctx->host_blob.data() : static_cast<const uint8_t*>(ctx->d_blob), B, P.walk);
+    keep_host_copies(ctx.get(), d, P.geom);
+    ctx->feat = sfeat | P.geom.feat;
     ctx->variant = tu.kernel == RTW_KERNEL_WAVEFRONT ? 2 : tu.kernel == RTW_KERNEL_PERSISTENT ? 1 : 0;
-    {
-        // wavefront batch capacity: up to 2^29 paths (BASELINE config 2 = 480M samples in one
-        // batch: one drain of long paths per render instead of one per 64M), within ~35 % of
-        // the device's FREE memory at scene creation (RTW_WF_PATH_BYTES per path); the
-        // allocation halves the batch on failure (run_wavefront)
-        size_t free_b = 0, total_b = 0;
-        uint64_t cap = 1ull << 29;
-        if (!host && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b)
-            cap = std::min<uint64_t>(cap, (uint64_t)(0.35 * (double)free_b) / RTW_WF_PATH_BYTES);
-        ctx->wf_max_paths = tu.wf_paths ? tu.wf_paths : std::max<uint64_t>(cap, 1u << 20);
-    }
-    // Round 5, with the dynamic tail (deal bit 2): fewer iterations before the tail pay everywhere but on
-    // image-textured scenes -- same-box A/B, 9 -> 4 iterations: C2 +3.7 %, C4 +3.3 %, Cornell +6.8 %, smoke
-    // +1.2 %, simple_light +1.9 %.  Image-textured scenes run no tail at all (every bounce a wavefront
-    // iteration: the launcher clamps to max_depth): C5 9 / 24 / 32 / 50 iterations 9425 / 9750 / 9816 / 9990
-    // Msamples/s (profiles/r5_iters/).
-    ctx->wf_iters = tu.wf_iters ? tu.wf_iters : (sfeat & RTW_F_IMAGE) ? (uint32_t)RTW_WF_MAX_ITERS : 4u;
-    ctx->wf_sort_iters = tu.sort_iters;
-    ctx->wf_sort_iters_split = tu.sort_iters_split;
-    ctx->wf_sort_mask = (1u << tu.sort_bits) - 1u;
-    {
-        int n_cu = 0;
-        if (host || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
-            n_cu < 1)
-            n_cu = 256;
-        ctx->n_cu = n_cu;
-    }
-    L.shade_min = tu.mega_shade_min;
-    L.waves = tu.mega_waves;
-    L.tile_order = tu.mega_tile_order ? 1u : 0u;
-    // (an unfiltered variant measured +-0 on C2 and -20 % on C4: its codegen slowed the L1/L2 walk)
-    L.fast_reject = tu.fast_reject ? 1u : 0u;
-    L.use_lds = orders == 1 && (tu.lds & RTW_LDS_MEGA_NODES) ? 1u : 0u;  // the octant copies do not fit the megakernel's stage
-    // wavefront trace: node array staged in LDS when one ordering fits (object scenes,
-    // reference trees; +2 % on Cornell); the 8 octant copies of SAH sphere trees do not
-    L.wf_lds = (tu.lds & RTW_LDS_NODES) ? 1u : 0u;
-    // small static sphere SAH trees: the compact nodes of all 8 orders in LDS (C2: +1 %)
-    L.wf_clds = (tu.lds & RTW_LDS_CNODES) ? 1u : 0u;
-    // compact LDS stage: gen, trace and shade of an iteration fused in one kernel
-    // (the ray/hit hand-off through HBM disappears), tail on the LDS stage
-    L.wf_fuse = tu.fuse & 7u;
-    // Perlin tables (7 KiB each) staged in LDS by the fused step when at most 4 (noise scenes)
-    L.perlin_lds = (ctx->feat & RTW_F_NOISE) && d->n_perlins <= 4 && (tu.lds & RTW_LDS_PERLIN) ? 1u : 0u;
-    // materials of sphere scenes staged in LDS by the compact-LDS fused step when they fit beside the
-    // nodes (wf_run_fused checks the total): hit_prep's material load stops waiting on L1/L2
-    L.mat_lds = (tu.lds & RTW_LDS_MATERIALS) ? (uint32_t)((d->n_materials * sizeof(rtw_dev_material) + 15) & ~size_t(15)) : 0u;
-    const size_t shade_bytes = (size_t)(o_perl - o_mats);
-    L.shade_lds = shade_bytes <= 8192 && (tu.lds & RTW_LDS_SHADE) ? (uint32_t)shade_bytes : 0u;
-    // quads, instance member lists and instances of small object scenes (Cornell: ~2 KiB) staged in LDS
-    // with the node array: the member loop's loads stop waiting on L1
-    const size_t geom_bytes = (size_t)(o_med - o_quad);
-    L.geom_lds = (ctx->feat & RTW_F_GEOM) && geom_bytes <= 16384 && (tu.lds & RTW_LDS_GEOMETRY) ? (uint32_t)geom_bytes : 0u;
-    // SAH trees: FMA slab test on the padded boxes (only enlarges the set of visited nodes;
-    // reference trees keep the exact aabb.zig walk)
-    L.fast_box = ctx->box_pad > 0 && tu.fast_box ? 1u : 0u;
-    L.inst_cull = (tu.object_tree & RTW_OTREE_NO_CULL) ? 0u : 1u;  // consulted only with fast_box
-    if (host) {  // the exact aabb.zig slab test and IEEE sphere test (the hardware estimates are device-only)
-        L.fast_box = 0;
-        L.fast_reject = 0;
-    }
-    ctx->cpu_threads = tu.cpu_threads;
-    ctx->grid = host ? 0 : rtw_persistent_grid(ctx->feat, (uint32_t)n_nodes, (int)L.waves, L.use_lds != 0);
 
-    ctx->stats.n_nodes = (uint32_t)n_nodes;
-    ctx->stats.n_leaves = d->objects ? d->n_objects : d->n_spheres;
-    ctx->stats.n_inner = (uint32_t)n_nodes - ctx->stats.n_leaves;
-    ctx->stats.depth = depth;
-    ctx->stats.device_bytes = off;
-    ctx->stats.axis_draws = draws;
-    ctx->stats.n_hoisted = n_hoisted;
-    ctx->stats.extent = ctx->extent;
-    ctx->stats.box_pad = ctx->box_pad;
-    *out = ctx;
+    set_stats(ctx.get(), d, orders, depth, draws, n_hoisted);
+    set_wavefront_knobs(ctx.get(), tu, sfeat);
+    set_launch_knobs(ctx.get(), d, tu, orders, B);
+    ctx->grid = host ? 0 : rtw_persistent_grid(ctx->feat, ctx->stats.n_nodes, ctx->base.use_lds != 0);
+    *out = ctx.release();
     return RTW_OK;
 }
 
@@ -564,8 +691,7 @@ void rtw_scene_destroy(rtw_ctx* ctx) {
 }
 
 int rtw_scene_flatten(const rtw_scene_desc* d, void* out, uint32_t cap, uint32_t* n_out, uint32_t* depth_out) {
-    if (!d || (d->n_spheres && !d->spheres) || (d->objects ? d->n_objects : d->n_spheres) == 0)
-        return fail(RTW_E_INVALID, "scene has no objects");
+    if (!d || !has_objects(d)) return fail(RTW_E_INVALID, "scene has no objects");
     std::vector<rtw_node> nodes;
     rtw_geometry geom;
     uint32_t depth = 0, draws = 0;
@@ -582,14 +708,14 @@ int rtw_scene_hash(rtw_ctx* ctx, uint64_t* out) {
     if (!ctx || !out) return fail(RTW_E_INVALID, "null ctx");
     // the scene image, then the registered lights in order (none: the image's hash as it was): a checkpoint
     // taken with lights is another estimator's partial sum than one taken without
+    std::lock_guard<std::mutex> lock(ctx->mu);  // the registrations write these vectors under it
     uint64_t h = ctx->scene_hash;
+    auto mix = [&h](uint32_t w) {
+        for (int b = 0; b < 4; b++) h = (h ^ ((w >> (8 * b)) & 0xFFu)) * 0x100000001B3ull;
+    };
     if (!ctx->lights.empty()) {
-        const uint32_t n = (uint32_t)ctx->lights.size();
-        auto mix = [&h](uint32_t w) {
-            for (int b = 0; b < 4; b++) h = (h ^ ((w >> (8 * b)) & 0xFFu)) * 0x100000001B3ull;
-        };
         mix(0x5447494Cu);  // "LIGT"
-        mix(n);
+        mix((uint32_t)ctx->lights.size());
         for (const rtw_object& o : ctx->lights) {
             mix(o.kind);
             mix(o.index);
@@ -597,9 +723,6 @@ int rtw_scene_hash(rtw_ctx* ctx, uint64_t* out) {
     }
     // then the registered vertex attributes (none: the hash as it was): another image
     if (!ctx->vattr_quads.empty()) {
-        auto mix = [&h](uint32_t w) {
-            for (int b = 0; b < 4; b++) h = (h ^ ((w >> (8 * b)) & 0xFFu)) * 0x100000001B3ull;
-        };
         mix(0x52545441u);  // "ATTR"
         mix((uint32_t)ctx->vattr_quads.size());
         for (size_t k = 0; k < ctx->vattr_quads.size(); k++) {
@@ -639,16 +762,16 @@ int rtw_scene_set_vertex_attrs(rtw_ctx* ctx, const uint32_t* quads, const rtw_ve
         seen[qi] = 1;
         const rtw_vertex_attr& a = attrs[k];
         if (a.flags & ~(uint32_t)(RTW_ATTR_NORMALS | RTW_ATTR_UVS)) {
-            std::snprintf(msg, sizeof msg, "rtw_scene_set_vertex_attrs: entry %u (quad %u): unknown flag bits 0x%x", k, qi,
-                          a.flags);
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_vertex_attrs: entry %u (quad %u): unknown flag bits 0x%x", k,
+                          qi, a.flags);
             return fail(RTW_E_INVALID, msg);
         }
         rtw_vertex_attr o{};
         o.flags = a.flags;
         if (a.flags & RTW_ATTR_NORMALS) {
             if (!rtw_vattr_normalise(a, o)) {
-                std::snprintf(msg, sizeof msg, "rtw_scene_set_vertex_attrs: entry %u (quad %u): a normal is not finite or "
-                              "has zero length", k, qi);
+                std::snprintf(msg, sizeof msg, "rtw_scene_set_vertex_attrs: entry %u (quad %u): a normal is not finite "
+                              "or has zero length", k, qi);
                 return fail(RTW_E_INVALID, msg);
             }
         }
@@ -656,8 +779,8 @@ int rtw_scene_set_vertex_attrs(rtw_ctx* ctx, const uint32_t* quads, const rtw_ve
             for (int c = 0; c < 3; c++)
                 for (int i = 0; i < 2; i++) {
                     if (!std::isfinite(a.uv[c][i])) {
-                        std::snprintf(msg, sizeof msg, "rtw_scene_set_vertex_attrs: entry %u (quad %u): a uv is not finite",
-                                      k, qi);
+                        std::snprintf(msg, sizeof msg, "rtw_scene_set_vertex_attrs: entry %u (quad %u): a uv is not "
+                                      "finite", k, qi);
                         return fail(RTW_E_INVALID, msg);
                     }
                     o.uv[c][i] = a.uv[c][i];
@@ -667,28 +790,18 @@ int rtw_scene_set_vertex_attrs(rtw_ctx* ctx, const uint32_t* quads, const rtw_ve
         static_assert(sizeof(rtw_dev_vattr) == sizeof(rtw_vertex_attr), "the device record is the public one");
         std::memcpy(&rec[qi], &o, sizeof o);
     }
-    const bool host = ctx->device == RTW_DEVICE_CPU;
-    if (!host) {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        HIP_TRY(hipSetDevice(ctx->device));
-        // a render left on a caller's stream (RTW_RENDER_NO_SYNC) may still read the records
-        if (ctx->last_done) HIP_TRY(hipEventSynchronize(ctx->last_done));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (n && !ctx->d_vattrs) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->d_vattrs), nq * sizeof(rtw_dev_vattr)));
-        if (n) HIP_TRY(hipMemcpy(ctx->d_vattrs, rec.data(), nq * sizeof(rtw_dev_vattr), hipMemcpyHostToDevice));
-        // the persistent kernel's resident grid is its instantiation's
-        ctx->grid = rtw_persistent_grid(ctx->feat | (ctx->base.n_lights ? RTW_F_PDF : 0u) | (n ? RTW_F_ATTR : 0u),
-                                        ctx->stats.n_nodes, (int)ctx->base.waves, ctx->base.use_lds != 0);
-    }
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    rtw_launch base = ctx->base;
+    if (int rc = publish_records(ctx, base, ctx->vattrs_rec, rec, &ctx->d_vattrs, nq, base.vattrs)) return rc;
     ctx->vattr_quads.assign(quads, quads + n);
     ctx->vattr_set = set;
-    ctx->vattrs_rec = rec;
-    ctx->base.vattrs = n ? (host ? ctx->vattrs_rec.data() : ctx->d_vattrs) : nullptr;
+    ctx->base = base;
     return RTW_OK;
 }
 
 int rtw_scene_vertex_attrs_get(rtw_ctx* ctx, uint32_t* quads, rtw_vertex_attr* attrs, uint32_t cap, uint32_t* n_out) {
     if (!ctx) return fail(RTW_E_INVALID, "null ctx");
+    std::lock_guard<std::mutex> lock(ctx->mu);
     const uint32_t n = (uint32_t)ctx->vattr_quads.size();
     if (n_out) *n_out = n;
     const uint32_t m = cap < n ? cap : n;
@@ -713,23 +826,27 @@ int rtw_scene_set_lights(rtw_ctx* ctx, const rtw_object* lights, uint32_t n) {
         const bool sph = o.kind == RTW_OBJ_SPHERE;
         const char* what = sph ? "sphere" : "quad";
         if (o.index >= (sph ? ctx->spheres_host.size() : ctx->quads_host.size())) {
-            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u: %s index %u out of range", k, what, o.index);
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u: %s index %u out of range", k, what,
+                          o.index);
             return fail(RTW_E_INVALID, msg);
         }
         if (sph && !(ctx->feat & RTW_F_GEOM)) {
             // sphere scenes walk octant copies, compact nodes, tile lists and hoisted spheres, which the
             // RTW_F_ALL | RTW_F_PDF kernels do not
-            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (sphere %u): a scene of spheres alone cannot "
-                          "register lights (its kernels have no mixture-density form; out of scope)", k, o.index);
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (sphere %u): a scene of spheres alone "
+                          "cannot register lights (its kernels have no mixture-density form; out of scope)", k,
+                          o.index);
             return fail(RTW_E_INVALID, msg);
         }
         const uint32_t ref = RTW_REF(o.kind, o.index);
         if (std::find(ctx->members_host.begin(), ctx->members_host.end(), ref) != ctx->members_host.end()) {
-            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (%s %u) is an instance member", k, what, o.index);
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (%s %u) is an instance member", k, what,
+                          o.index);
             return fail(RTW_E_INVALID, msg);
         }
         if (std::find(ctx->boundaries_host.begin(), ctx->boundaries_host.end(), ref) != ctx->boundaries_host.end()) {
-            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (%s %u) is a medium boundary", k, what, o.index);
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (%s %u) is a medium boundary", k, what,
+                          o.index);
             return fail(RTW_E_INVALID, msg);
         }
         bool top = false;  // a leaf of the world tree (the first ordering: object scenes keep one)
@@ -741,8 +858,8 @@ int rtw_scene_set_lights(rtw_ctx* ctx, const rtw_object* lights, uint32_t n) {
             top = (aw & RTW_LEAF_BIT) && RTW_LEAF_KIND(bw) == o.kind && bz == o.index;
         }
         if (!top) {
-            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (%s %u) is not in the scene's object list", k,
-                          what, o.index);
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (%s %u) is not in the scene's object list",
+                          k, what, o.index);
             return fail(RTW_E_INVALID, msg);
         }
         const uint32_t mat = sph ? ctx->spheres_host[o.index].mat : RTW_QUAD_MAT(ctx->quads_host[o.index].mat);
@@ -766,8 +883,8 @@ int rtw_scene_set_lights(rtw_ctx* ctx, const rtw_object* lights, uint32_t n) {
                 return fail(RTW_E_INVALID, msg);
             }
             if (!(s.radius > 0.0f) || !std::isfinite(s.radius)) {
-                std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (sphere %u) has no finite positive radius",
-                              k, o.index);
+                std::snprintf(msg, sizeof msg, "rtw_scene_set_lights: light %u (sphere %u) has no finite positive "
+                              "radius", k, o.index);
                 return fail(RTW_E_INVALID, msg);
             }
             rec[k].radius = s.radius;
@@ -787,28 +904,19 @@ int rtw_scene_set_lights(rtw_ctx* ctx, const rtw_object* lights, uint32_t n) {
         rec[k].quad = o.index;
         rec[k].area = area;
     }
-    const bool host = ctx->device == RTW_DEVICE_CPU;
-    if (!host) {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        HIP_TRY(hipSetDevice(ctx->device));
-        // a render left on a caller's stream (RTW_RENDER_NO_SYNC) may still read the records
-        if (ctx->last_done) HIP_TRY(hipEventSynchronize(ctx->last_done));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (n && !ctx->d_lights) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->d_lights), RTW_MAX_LIGHTS * sizeof(rtw_dev_light)));
-        if (n) HIP_TRY(hipMemcpy(ctx->d_lights, rec.data(), n * sizeof(rtw_dev_light), hipMemcpyHostToDevice));
-        // the persistent kernel's resident grid is its instantiation's
-        ctx->grid = rtw_persistent_grid(ctx->feat | (n ? RTW_F_PDF : 0u) | (ctx->base.vattrs ? RTW_F_ATTR : 0u),
-                                        ctx->stats.n_nodes, (int)ctx->base.waves, ctx->base.use_lds != 0);
-    }
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    rtw_launch base = ctx->base;
+    base.n_lights = n;
+    if (int rc = publish_records(ctx, base, ctx->lights_rec, rec, &ctx->d_lights, RTW_MAX_LIGHTS, base.lights))
+        return rc;
     ctx->lights.assign(lights, lights + n);
-    ctx->lights_rec = rec;
-    ctx->base.n_lights = n;
-    ctx->base.lights = n ? (host ? ctx->lights_rec.data() : ctx->d_lights) : nullptr;
+    ctx->base = base;
     return RTW_OK;
 }
 
 int rtw_scene_lights_get(rtw_ctx* ctx, rtw_object* out, uint32_t cap, uint32_t* n_out) {
     if (!ctx) return fail(RTW_E_INVALID, "null ctx");
+    std::lock_guard<std::mutex> lock(ctx->mu);
     const uint32_t n = (uint32_t)ctx->lights.size();
     if (n_out) *n_out = n;
     if (out && n) std::memcpy(out, ctx->lights.data(), sizeof(rtw_object) * (cap < n ? cap : n));
@@ -872,7 +980,9 @@ rtw_launch make_launch(const rtw_ctx* ctx, const rtw_camera* c, uint64_t seed) {
     return L;
 }
 
-uint32_t auto_batch(const rtw_ctx* ctx, uint64_t pixels, uint32_t spp) {
+}  // namespace
+
+uint32_t rtw_auto_batch(const rtw_ctx* ctx, uint64_t pixels, uint32_t spp) {
     // ~64M samples per launch (the wavefront: its batch capacity): long enough to
     // amortise the launches, short enough to poll cancel
     const uint64_t target = ctx->variant == 2 ? ctx->wf_max_paths : (64ull << 20);
@@ -882,12 +992,21 @@ uint32_t auto_batch(const rtw_ctx* ctx, uint64_t pixels, uint32_t spp) {
     return (uint32_t)b;
 }
 
-int validate_cam(const rtw_camera* cam) {
+int rtw_validate_cam(const rtw_camera* cam) {
     if (!cam) return fail(RTW_E_INVALID, "null camera");
     if (cam->image_width == 0 || cam->image_height == 0) return fail(RTW_E_INVALID, "camera not initialised");
     if ((uint64_t)cam->image_width * cam->image_height > 0xFFFFFFFFull) return fail(RTW_E_INVALID, "image too large");
     return RTW_OK;
 }
+
+// the ABI-5 options of the host-buffer entry points: stop/progress and spp_batch only
+int rtw_check_host_opts(const rtw_render_opts* o) {
+    if (o && (o->flags || o->counters || o->timing))
+        return fail(RTW_E_INVALID, "host-buffer render: flags, counters and timing must be 0/NULL");
+    return RTW_OK;
+}
+
+namespace {
 
 // Bytes of the wavefront state run_wavefront takes from one allocation: per slot set (two) the ray_o, ray_d,
 // thr, acc streams (16 B) and rng (8 B); the hit records (8 B) by slot; the radiance (12 B) by path; the three
@@ -897,7 +1016,8 @@ size_t wf_state_bytes(uint64_t Q, uint64_t P) {
     return 2 * (4 * al(Q * 16) + al(Q * 8)) + al(Q * 8) + al(P * sizeof(rtw_rgb)) +
            3 * al((uint64_t)RTW_WF_STRIPES * RTW_WF_LEN_STRIDE * 4) + al(RTW_WF_DEAL_COUNTERS * 4);
 }
-static_assert(RTW_WF_PATH_BYTES == 2 * (4 * 16 + 8) + 8 + sizeof(rtw_rgb), "RTW_WF_PATH_BYTES = wf_state_bytes per path");
+static_assert(RTW_WF_PATH_BYTES == 2 * (4 * 16 + 8) + 8 + sizeof(rtw_rgb),
+              "RTW_WF_PATH_BYTES = wf_state_bytes per path");
 
 // Wavefront (v2) render of samples [L.s0, L.s1): batches of n_s samples so that
 // n_pix * n_s paths fit the path-state buffer (grown on demand, kept in the ctx).
@@ -915,7 +1035,8 @@ int run_wavefront(rtw_ctx* ctx, rtw_launch L, hipStream_t stream, rtw_timer* T) 
     const uint64_t max_waves = rtw_wavefront_max_waves(ctx->n_cu);
     // + direction-bucketed iterations: every wave of a stripe may leave one partly filled 64-slot block per
     //   bucket (wf_push_bucketed)
-    const uint64_t bucket_blocks = (ctx->wf_sort_iters || ctx->wf_sort_iters_split) ? (max_waves / RTW_WF_STRIPES + 1) * RTW_WF_BUCKETS : 0;
+    const bool bucketed = ctx->wf_sort_iters || ctx->wf_sort_iters_split;
+    const uint64_t bucket_blocks = bucketed ? (max_waves / RTW_WF_STRIPES + 1) * RTW_WF_BUCKETS : 0;
     // + the dynamic deal of iteration 0 (rtw_tuning.deal bit 1): a stripe group claims whole runs of 16 chunks
     //   and then singles, so it may end up to one run and one single chunk above its even share (RUN + 1), whatever
     //   the grid's waves per stripe (a device or partition with few CUs)
@@ -926,15 +1047,9 @@ int run_wavefront(rtw_ctx* ctx, rtw_launch L, hipStream_t stream, rtw_timer* T) 
     // slots per set: every path (iteration 0: slot = path id) or every stripe's capacity
     auto slots = [&](uint64_t paths) { return std::max<uint64_t>(paths, stripe_cap(paths) * RTW_WF_STRIPES); };
     if (ctx->wf_cap < need) {
-        if (ctx->d_wf) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            (void)hipFree(ctx->d_wf);
-        }
-        ctx->d_wf = nullptr;
-        ctx->wf_cap = 0;
         for (;;) {  // device memory taken since scene creation (other contexts, torch): halve the batch
             const size_t bytes = wf_state_bytes(slots(need), need);
-            const hipError_t e = hipMalloc(&ctx->d_wf, bytes);
+            const hipError_t e = rtw_device_grow(&ctx->d_wf, &ctx->wf_cap, need, bytes, stream);
             if (e == hipSuccess) break;
             if (e != hipErrorOutOfMemory || n_s == 1) return hip_fail(e, "wavefront path state");
             (void)hipGetLastError();  // clear the sticky OOM before the retry
@@ -942,7 +1057,6 @@ int run_wavefront(rtw_ctx* ctx, rtw_launch L, hipStream_t stream, rtw_timer* T) 
             need = n_pix * n_s;
             ctx->wf_max_paths = need;  // later renders start from the size that fit
         }
-        ctx->wf_cap = need;
     }
     if (n_s * n_pix > ctx->wf_cap) n_s = std::max<uint64_t>(1, ctx->wf_cap / n_pix);
     const uint64_t P = ctx->wf_cap, Q = slots(P);
@@ -977,16 +1091,9 @@ int run_wavefront(rtw_ctx* ctx, rtw_launch L, hipStream_t stream, rtw_timer* T) 
     // camera-ray candidate lists (the compact-LDS fused step of static sphere scenes, rtw_tuning.tile_lists)
     if (L.tile_lists && L.cnodes && L.n_orders >= 4) {
         const uint64_t tiles = n_pix / 64;
-        if (ctx->tl_cap < tiles) {
-            if (ctx->d_tl) {
-                HIP_TRY(hipStreamSynchronize(stream));
-                (void)hipFree(ctx->d_tl);
-            }
-            ctx->d_tl = nullptr;
-            ctx->tl_cap = 0;
-            if (hipMalloc(&ctx->d_tl, tiles * RTW_TL_BYTES + 256) == hipSuccess) ctx->tl_cap = tiles;
-            else (void)hipGetLastError();  // no lists: the walk
-        }
+        if (ctx->tl_cap < tiles &&
+            rtw_device_grow(&ctx->d_tl, &ctx->tl_cap, tiles, tiles * RTW_TL_BYTES + 256, stream) != hipSuccess)
+            (void)hipGetLastError();  // no lists: the walk
         if (ctx->tl_cap >= tiles) {
             W.tl = static_cast<uint4*>(ctx->d_tl);
             W.tl_count = reinterpret_cast<uint32_t*>(static_cast<char*>(ctx->d_tl) + tiles * RTW_TL_MAX * 32);
@@ -1071,13 +1178,6 @@ int run_host(rtw_ctx* ctx, rtw_launch L, uint32_t begin, uint32_t end, uint32_t 
     return RTW_OK;
 }
 
-// the ABI-5 options of the host-buffer entry points: stop/progress and spp_batch only
-int check_host_opts(const rtw_render_opts* o) {
-    if (o && (o->flags || o->counters || o->timing))
-        return fail(RTW_E_INVALID, "host-buffer render: flags, counters and timing must be 0/NULL");
-    return RTW_OK;
-}
-
 // Synchronise and sum the timer's events per kernel kind into `out`.
 int harvest_timing(rtw_ctx* ctx, rtw_timer& T, rtw_kernel_timing* out) {
     HIP_TRY(hipStreamSynchronize(T.stream));
@@ -1104,14 +1204,7 @@ void set_tiles(rtw_launch& L) {
 // the context's device staging buffer of the host-buffer entry points, >= bytes
 int ensure_scratch(rtw_ctx* ctx, size_t bytes) {
     if (ctx->scratch_bytes >= bytes) return RTW_OK;
-    if (ctx->d_scratch) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->d_scratch);
-    }
-    ctx->d_scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&ctx->d_scratch, bytes));
-    ctx->scratch_bytes = bytes;
+    HIP_TRY(rtw_device_grow(&ctx->d_scratch, &ctx->scratch_bytes, bytes, bytes, ctx->stream));
     return RTW_OK;
 }
 
@@ -1124,6 +1217,40 @@ int stream_leave(rtw_ctx* ctx, hipStream_t s) {
     if (!ctx->last_done) HIP_TRY(hipEventCreateWithFlags(&ctx->last_done, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(ctx->last_done, s));
     ctx->last_stream = s;
+    return RTW_OK;
+}
+
+// the launch's work fields for the pixels [pix_begin, pix_end) of the image (plain mode: no shards)
+void set_plain_range(rtw_launch& L, uint32_t pix_begin, uint32_t pix_end) {
+    L.pix_begin = pix_begin;
+    L.pix_end = pix_end;
+    L.row0 = pix_begin / L.W;
+    L.n_rows = (pix_end - 1) / L.W - L.row0 + 1;
+    L.n_shards = 0;
+    set_tiles(L);
+}
+
+bool shard_spec_ok(uint32_t rpb, uint32_t n_shards, uint32_t shard) {
+    return (rpb & ~RTW_ROWS_FLAGS) && n_shards && shard < n_shards;
+}
+
+// Enqueue the device render of samples [spp_begin, spp_end) of the prepared launch on stream s and finish the
+// call (the caller holds ctx->mu and has entered the stream): opts' counters, batch size, timing and
+// RTW_RENDER_NO_SYNC; `pixels` is what the progress callback and the automatic batch count.
+int enqueue_and_finish(rtw_ctx* ctx, rtw_launch& L, uint32_t spp_begin, uint32_t spp_end, hipStream_t s,
+                       const rtw_render_opts* opts, uint64_t pixels) {
+    L.counters = opts ? reinterpret_cast<unsigned long long*>(opts->counters) : nullptr;
+    const uint32_t batch = opts && opts->spp_batch ? opts->spp_batch : rtw_auto_batch(ctx, pixels, spp_end - spp_begin);
+    rtw_timer T;
+    T.stream = s;
+    T.pool.swap(ctx->ev_pool);
+    rtw_timer* tp = (opts && opts->timing) ? &T : nullptr;
+    int rc = run_batches(ctx, L, spp_begin, spp_end, batch, s, opts, pixels, tp);
+    ctx->ev_pool.swap(T.pool);
+    if (int rl = stream_leave(ctx, s)) return rl;
+    if (tp && rc == RTW_OK) rc = harvest_timing(ctx, T, opts->timing);
+    if (rc) return rc;
+    if (!(opts && (opts->flags & RTW_RENDER_NO_SYNC))) HIP_TRY(hipStreamSynchronize(s));
     return RTW_OK;
 }
 
@@ -1142,20 +1269,8 @@ int render_rows_locked(rtw_ctx* ctx, const rtw_camera* cam, uint32_t rpb, uint32
     L.shard = shard;
     L.pix_begin = 0;
     L.pix_end = cam->size;
-    L.counters = opts ? reinterpret_cast<unsigned long long*>(opts->counters) : nullptr;
     set_tiles(L);
-    uint32_t batch = opts && opts->spp_batch ? opts->spp_batch : auto_batch(ctx, (uint64_t)rows * cam->image_width, spp_end - spp_begin);
-    rtw_timer T;
-    T.stream = s;
-    T.pool.swap(ctx->ev_pool);
-    rtw_timer* tp = (opts && opts->timing) ? &T : nullptr;
-    int rc = run_batches(ctx, L, spp_begin, spp_end, batch, s, opts, (uint64_t)rows * cam->image_width, tp);
-    ctx->ev_pool.swap(T.pool);
-    if (int rl = stream_leave(ctx, s)) return rl;
-    if (tp && rc == RTW_OK) rc = harvest_timing(ctx, T, opts->timing);
-    if (rc) return rc;
-    if (!(opts && (opts->flags & RTW_RENDER_NO_SYNC))) HIP_TRY(hipStreamSynchronize(s));
-    return RTW_OK;
+    return enqueue_and_finish(ctx, L, spp_begin, spp_end, s, opts, (uint64_t)rows * cam->image_width);
 }
 
 }  // namespace
@@ -1175,8 +1290,8 @@ int rtw_render(rtw_ctx* ctx, const rtw_camera* cam, uint32_t pix_begin, uint32_t
 int rtw_render_ex(rtw_ctx* ctx, const rtw_camera* cam, uint32_t pix_begin, uint32_t pix_end, uint32_t spp_begin,
                   uint32_t spp_end, uint64_t seed, float* accum, const rtw_render_opts* opts) {
     if (!ctx || !accum) return fail(RTW_E_INVALID, "null ctx/accum");
-    if (int rc = validate_cam(cam)) return rc;
-    if (int rc = check_host_opts(opts)) return rc;
+    if (int rc = rtw_validate_cam(cam)) return rc;
+    if (int rc = rtw_check_host_opts(opts)) return rc;
     if (pix_end > cam->size || pix_begin > pix_end) return fail(RTW_E_INVALID, "pixel range out of image");
     if (spp_begin > spp_end) return fail(RTW_E_INVALID, "bad sample range");
     if (pix_begin == pix_end || spp_begin == spp_end) return RTW_OK;
@@ -1212,7 +1327,7 @@ int rtw_render_ex(rtw_ctx* ctx, const rtw_camera* cam, uint32_t pix_begin, uint3
         if (int rc = stream_leave(ctx, ctx->stream)) return rc;
         HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));  // (last: no early return leaks it)
         ctx->host_calls++;
-        batch = ubatch ? ubatch : auto_batch(ctx, pixels, spp_end - spp_begin);
+        batch = ubatch ? ubatch : rtw_auto_batch(ctx, pixels, spp_end - spp_begin);
     }
     const bool polled = rtw_polled(opts);
     const uint64_t total = pixels * (uint64_t)(spp_end - spp_begin);
@@ -1231,13 +1346,8 @@ int rtw_render_ex(rtw_ctx* ctx, const rtw_camera* cam, uint32_t pix_begin, uint3
             }
             rtw_launch L = make_launch(ctx, cam, seed);
             L.accum = reinterpret_cast<float4*>(ctx->d_scratch);
-            L.pix_begin = pix_begin;
-            L.pix_end = pix_end;
-            L.row0 = pix_begin / cam->image_width;
-            L.n_rows = (pix_end - 1) / cam->image_width - L.row0 + 1;
-            L.n_shards = 0;
             L.counters = nullptr;
-            set_tiles(L);
+            set_plain_range(L, pix_begin, pix_end);
             rc = run_batches(ctx, L, s, s_end, s_end - s, ctx->stream, nullptr, pixels);
             if (rc == RTW_OK) rc = stream_leave(ctx, ctx->stream);
             if (rc == RTW_OK && hipEventRecord(done, ctx->stream) != hipSuccess) rc = fail(RTW_E_HIP, "event");
@@ -1275,7 +1385,7 @@ int rtw_render_device(rtw_ctx* ctx, const rtw_camera* cam, uint32_t pix_begin, u
                       uint32_t spp_end, uint64_t seed, float* d_accum, void* stream, const rtw_render_opts* opts) {
     if (!ctx || !d_accum) return fail(RTW_E_INVALID, "null ctx/accum");
     if (ctx->device == RTW_DEVICE_CPU) return fail(RTW_E_INVALID, "host context: use rtw_render");
-    if (int rc = validate_cam(cam)) return rc;
+    if (int rc = rtw_validate_cam(cam)) return rc;
     if (pix_end > cam->size || pix_begin > pix_end) return fail(RTW_E_INVALID, "pixel range out of image");
     if (spp_begin > spp_end) return fail(RTW_E_INVALID, "bad sample range");
     if (pix_begin == pix_end || spp_begin == spp_end) return RTW_OK;
@@ -1285,29 +1395,12 @@ int rtw_render_device(rtw_ctx* ctx, const rtw_camera* cam, uint32_t pix_begin, u
     if (int rc = stream_enter(ctx, s)) return rc;
     rtw_launch L = make_launch(ctx, cam, seed);
     L.accum = reinterpret_cast<float4*>(d_accum);
-    L.pix_begin = pix_begin;
-    L.pix_end = pix_end;
-    L.row0 = pix_begin / cam->image_width;
-    L.n_rows = (pix_end - 1) / cam->image_width - L.row0 + 1;
-    L.n_shards = 0;
-    L.counters = opts ? reinterpret_cast<unsigned long long*>(opts->counters) : nullptr;
-    set_tiles(L);
-    uint32_t batch = opts && opts->spp_batch ? opts->spp_batch : auto_batch(ctx, pix_end - pix_begin, spp_end - spp_begin);
-    rtw_timer T;
-    T.stream = s;
-    T.pool.swap(ctx->ev_pool);
-    rtw_timer* tp = (opts && opts->timing) ? &T : nullptr;
-    int rc = run_batches(ctx, L, spp_begin, spp_end, batch, s, opts, pix_end - pix_begin, tp);
-    ctx->ev_pool.swap(T.pool);
-    if (int rl = stream_leave(ctx, s)) return rl;
-    if (tp && rc == RTW_OK) rc = harvest_timing(ctx, T, opts->timing);
-    if (rc) return rc;
-    if (!(opts && (opts->flags & RTW_RENDER_NO_SYNC))) HIP_TRY(hipStreamSynchronize(s));
-    return RTW_OK;
+    set_plain_range(L, pix_begin, pix_end);
+    return enqueue_and_finish(ctx, L, spp_begin, spp_end, s, opts, pix_end - pix_begin);
 }
 
 uint32_t rtw_shard_rows(uint32_t H, uint32_t rpb, uint32_t n_shards, uint32_t shard) {
-    if (!(rpb & ~RTW_ROWS_FLAGS) || !n_shards || shard >= n_shards) return 0;
+    if (!shard_spec_ok(rpb, n_shards, shard)) return 0;
     uint32_t rows = 0;
     const uint32_t t = rtw_shard_tile_rows(H, rpb, n_shards, shard);
     for (uint32_t r = 0; r < t; r++) rows += rtw_shard_row(H, rpb, n_shards, shard, r) < H ? 1u : 0u;
@@ -1315,12 +1408,12 @@ uint32_t rtw_shard_rows(uint32_t H, uint32_t rpb, uint32_t n_shards, uint32_t sh
 }
 
 uint32_t rtw_shard_image_row(uint32_t rpb, uint32_t n_shards, uint32_t shard, uint32_t tile_row) {
-    if (!rpb || (rpb & RTW_ROWS_FLAGS) || !n_shards || shard >= n_shards) return 0xFFFFFFFFu;
+    if (!shard_spec_ok(rpb, n_shards, shard) || (rpb & RTW_ROWS_FLAGS)) return 0xFFFFFFFFu;  // plain shards only
     return rtw_tile_row_image(rpb, n_shards, shard, tile_row);
 }
 
 uint32_t rtw_shard_image_row_h(uint32_t H, uint32_t rpb, uint32_t n_shards, uint32_t shard, uint32_t tile_row) {
-    if (!(rpb & ~RTW_ROWS_FLAGS) || !n_shards || shard >= n_shards) return 0xFFFFFFFFu;
+    if (!shard_spec_ok(rpb, n_shards, shard)) return 0xFFFFFFFFu;
     return rtw_shard_row(H, rpb, n_shards, shard, tile_row);
 }
 
@@ -1329,8 +1422,8 @@ int rtw_render_rows_device(rtw_ctx* ctx, const rtw_camera* cam, uint32_t rpb, ui
                            const rtw_render_opts* opts) {
     if (!ctx || !d_tile) return fail(RTW_E_INVALID, "null ctx/tile");
     if (ctx->device == RTW_DEVICE_CPU) return fail(RTW_E_INVALID, "host context: use rtw_render_rows");
-    if (int rc = validate_cam(cam)) return rc;
-    if (!(rpb & ~RTW_ROWS_FLAGS) || !n_shards || shard >= n_shards) return fail(RTW_E_INVALID, "bad shard spec");
+    if (int rc = rtw_validate_cam(cam)) return rc;
+    if (!shard_spec_ok(rpb, n_shards, shard)) return fail(RTW_E_INVALID, "bad shard spec");
     if (spp_begin > spp_end) return fail(RTW_E_INVALID, "bad sample range");
     const uint32_t rows = rtw_shard_rows(cam->image_height, rpb, n_shards, shard);
     if (rows == 0 || spp_begin == spp_end) return RTW_OK;
@@ -1344,9 +1437,9 @@ int rtw_render_rows_device(rtw_ctx* ctx, const rtw_camera* cam, uint32_t rpb, ui
 int rtw_render_rows(rtw_ctx* ctx, const rtw_camera* cam, uint32_t rpb, uint32_t n_shards, uint32_t shard,
                     uint32_t spp_begin, uint32_t spp_end, uint64_t seed, float* tile, const rtw_render_opts* opts) {
     if (!ctx || !tile) return fail(RTW_E_INVALID, "null ctx/tile");
-    if (int rc = validate_cam(cam)) return rc;
-    if (int rc = check_host_opts(opts)) return rc;
-    if (!(rpb & ~RTW_ROWS_FLAGS) || !n_shards || shard >= n_shards) return fail(RTW_E_INVALID, "bad shard spec");
+    if (int rc = rtw_validate_cam(cam)) return rc;
+    if (int rc = rtw_check_host_opts(opts)) return rc;
+    if (!shard_spec_ok(rpb, n_shards, shard)) return fail(RTW_E_INVALID, "bad shard spec");
     if (spp_begin > spp_end) return fail(RTW_E_INVALID, "bad sample range");
     const uint32_t rows = rtw_shard_rows(cam->image_height, rpb, n_shards, shard);
     if (rows == 0 || spp_begin == spp_end) return RTW_OK;
@@ -1365,16 +1458,7 @@ int rtw_render_rows(rtw_ctx* ctx, const rtw_camera* cam, uint32_t rpb, uint32_t 
     // the tile is staged in its own buffer, never in d_scratch: rtw_render_ex calls on this context release
     // the lock between batches with their chunks staged there
     const size_t nb = (size_t)rows * W * 16;
-    if (ctx->rows_bytes < nb) {
-        if (ctx->d_rows) {
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            (void)hipFree(ctx->d_rows);
-        }
-        ctx->d_rows = nullptr;
-        ctx->rows_bytes = 0;
-        HIP_TRY(hipMalloc(&ctx->d_rows, nb));
-        ctx->rows_bytes = nb;
-    }
+    if (ctx->rows_bytes < nb) HIP_TRY(rtw_device_grow(&ctx->d_rows, &ctx->rows_bytes, nb, nb, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->d_rows, tile, nb, hipMemcpyHostToDevice, ctx->stream));
     rtw_render_opts ctl{};
     if (opts) ctl = *opts;
@@ -1422,7 +1506,7 @@ int rtw_debug_sample(rtw_ctx* ctx, const rtw_camera* cam, uint64_t seed, uint32_
                      float out[3]) {
     if (!ctx || !out) return fail(RTW_E_INVALID, "null args");
     if (ctx->device == RTW_DEVICE_CPU) return fail(RTW_E_INVALID, "host context");
-    if (int rc = validate_cam(cam)) return rc;
+    if (int rc = rtw_validate_cam(cam)) return rc;
     if (pixel >= cam->size) return fail(RTW_E_INVALID, "pixel out of range");
     std::lock_guard<std::mutex> lock(ctx->mu);
     HIP_TRY(hipSetDevice(ctx->device));

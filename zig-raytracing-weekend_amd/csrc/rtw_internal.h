@@ -8,6 +8,7 @@
 #include <condition_variable>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -140,10 +141,78 @@ struct rtw_kernel_info {
 inline uint32_t rtw_feat_of(const rtw_launch& L) {
     return L.feat | (L.n_lights ? RTW_F_PDF : 0u) | (L.vattrs ? RTW_F_ATTR : 0u);
 }
-int rtw_persistent_grid(uint32_t feat, uint32_t n_nodes, int waves, bool use_lds);
+// What the registered features make of a feature set, the rule every dispatcher opens with (pick_feat below, the
+// wavefront's wf_pick_feat): vertex attributes run on top of every feature and the instance trees (a scene without
+// a tree runs them too: inst_hit_t falls back to the member loop), with or without the lights' mixture density;
+// lights on top of every feature; instance trees (inst_tree_t) likewise.  0: none of the three bits is set.
+// RTW_F_TREE is only ever set on top of RTW_F_ALL, so a dispatcher's "checker only" rule never sees it: testing
+// TREE before that rule (here) or after it picks the same class.
+inline uint32_t rtw_feat_prefix(uint32_t f) {
+    if (f & RTW_F_ATTR) return RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR | (f & RTW_F_PDF);
+    if (f & RTW_F_PDF) return RTW_F_ALL | (f & RTW_F_TREE) | RTW_F_PDF;
+    return (f & RTW_F_TREE) ? (RTW_F_ALL | RTW_F_TREE) : 0u;
+}
+// The class of the per-sample kernels (render_pixels_v0, render_persistent_v1, debug_sample_kernel, the host
+// backend's sample loop): the prefix, the two sphere-scene classes, else every feature.
+inline uint32_t rtw_pick_feat(uint32_t f) {
+    if (const uint32_t p = rtw_feat_prefix(f)) return p;
+    if ((f & ~RTW_F_CHECKER) == 0) return f ? RTW_F_CHECKER : 0u;
+    return RTW_F_ALL;
+}
+// The class table of those kernels: visit(c, f) calls f(std::integral_constant<uint32_t, c>) if c is listed.
+template <uint32_t... C>
+struct RtwClasses {
+    template <typename F>
+    static bool visit(uint32_t c, F&& f) {
+        return ((c == C && (f(std::integral_constant<uint32_t, C>{}), true)) || ...);
+    }
+};
+using RtwObjectClasses =
+    RtwClasses<RTW_F_ALL, RTW_F_ALL | RTW_F_TREE, RTW_F_ALL | RTW_F_PDF, RTW_F_ALL | RTW_F_TREE | RTW_F_PDF,
+               RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR, RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>;
+using RtwSphereClasses = RtwClasses<0u, RTW_F_CHECKER>;
+// Calls f with the class of the features `feat` (rtw_feat_of): one of the six object classes, or with SPHERES
+// (the persistent kernel) also one of the two sphere-scene classes, which the other kernels run as RTW_F_ALL.
+template <bool SPHERES, typename F>
+void rtw_with_class(uint32_t feat, F&& f) {
+    const uint32_t c = rtw_pick_feat(SPHERES ? feat : feat | RTW_F_ALL);
+    if constexpr (SPHERES) {
+        if (RtwSphereClasses::visit(c, f)) return;
+    }
+    (void)RtwObjectClasses::visit(c, f);
+}
+// ... and with a runtime bool as a std::bool_constant (the persistent kernel's LDS stage)
+template <typename F>
+void rtw_with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+int rtw_persistent_grid(uint32_t feat, uint32_t n_nodes, bool use_lds);
 
 void rtw_launch_render(const rtw_launch& L, void* stream, int variant, int grid);
 void rtw_set_error(const char* msg);  // the thread's rtw_last_error() message (rtw_host.hip)
+// Checks the render entry points of rtw_host.hip and rtw_multi.hip share (they set the error message): the camera
+// is non-null and initialised and its image addressable; the host-buffer entry points' options hold stop / progress
+// and spp_batch only.  And the automatic batch: samples per launch of `pixels` pixels, at most spp.
+struct rtw_ctx;
+int rtw_validate_cam(const rtw_camera* cam);
+int rtw_check_host_opts(const rtw_render_opts* o);
+uint32_t rtw_auto_batch(const rtw_ctx* ctx, uint64_t pixels, uint32_t spp);
+// A device buffer that grows on demand: replaces *buf (after the work on `s` that may still use it) by a fresh
+// allocation of `bytes` and sets *size -- the caller's measure of it -- to new_size.  If the allocation fails *buf
+// is null and *size 0; the caller clears or reports the error.
+template <typename T, typename N>
+hipError_t rtw_device_grow(T** buf, N* size, N new_size, size_t bytes, hipStream_t s) {
+    if (*buf) {
+        if (const hipError_t e = hipStreamSynchronize(s)) return e;
+        (void)hipFree(*buf);
+    }
+    *buf = nullptr;
+    *size = 0;
+    if (const hipError_t e = hipMalloc(reinterpret_cast<void**>(buf), bytes)) return e;
+    *size = new_size;
+    return hipSuccess;
+}
 // ABI-5 stop flags of rtw_render_opts: RenderThread.running (a Zig bool, 0 = stop) or cancel (non-zero = stop)
 inline bool rtw_stop_requested(const rtw_render_opts* o) {
     return o && ((o->running && *o->running == 0) || (o->cancel && *o->cancel != 0));

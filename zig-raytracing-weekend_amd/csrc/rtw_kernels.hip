@@ -395,39 +395,16 @@ __global__ void debug_sample_kernel(rtw_launch L, uint32_t pixel, uint32_t sampl
     }
 }
 
-template <uint32_t FEAT, bool LDS, int WAVES>
-void launch_v1(const rtw_launch& L, hipStream_t stream, int grid) {
-    const size_t lds = LDS ? (size_t)L.n_nodes * 32 : 0;
-    hipLaunchKernelGGL((render_persistent_v1<FEAT, LDS, WAVES>), dim3(grid), dim3(256), lds, stream, L);
-}
+// the persistent kernel stages the node array in LDS when one ordering fits (48 KiB)
+bool v1_lds(uint32_t n_nodes, uint32_t use_lds) { return n_nodes <= RTW_MEGA_LDS_NODES_MAX && use_lds; }
 
-template <uint32_t FEAT, bool LDS, int WAVES>
-int occupancy_v1(size_t lds_bytes) {
-    int b = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, render_persistent_v1<FEAT, LDS, WAVES>, 256,
-                                                     LDS ? lds_bytes : 0) != hipSuccess)
-        b = 1;
-    return b < 1 ? 1 : b;
-}
-
-uint32_t pick_feat(uint32_t f) {
-    // vertex attributes registered (rtw_feat_of): their two instantiations, on top of every feature and the trees
-    if (f & RTW_F_ATTR) return RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR | (f & RTW_F_PDF);
-    // lights registered (rtw_feat_of): the mixture-density instantiations, on top of every feature
-    if (f & RTW_F_PDF) return (f & RTW_F_TREE) ? (RTW_F_ALL | RTW_F_TREE | RTW_F_PDF) : (RTW_F_ALL | RTW_F_PDF);
-    if ((f & ~RTW_F_CHECKER) == 0) return f ? RTW_F_CHECKER : 0u;
-    return (f & RTW_F_TREE) ? (RTW_F_ALL | RTW_F_TREE) : RTW_F_ALL;  // instance trees: their own instantiation
-}
-
-
-// (launch-bound variants forcing 6 or 8 waves/SIMD spilled and were slower: removed)
-template <uint32_t FEAT, bool LDS>
-void launch_waves(const rtw_launch& L, hipStream_t st, int grid, int) {
-    launch_v1<FEAT, LDS, 1>(L, st, grid);
-}
-template <uint32_t FEAT, bool LDS>
-int occ_waves(size_t lds, int) {
-    return occupancy_v1<FEAT, LDS, 1>(lds);
+// the persistent kernel of a class (rtw_with_class) with or without the LDS stage (rtw_with_bool): f gets it as a
+// pointer.  (Launch-bound variants forcing 6 or 8 waves/SIMD spilled and were slower: removed; WAVES stays 1.)
+template <typename F>
+void with_v1(uint32_t feat, bool lds, F&& f) {
+    rtw_with_class<true>(feat, [&](auto c) {
+        rtw_with_bool(lds, [&](auto l) { f(render_persistent_v1<decltype(c)::value, decltype(l)::value, 1>); });
+    });
 }
 
 }  // namespace
@@ -435,90 +412,30 @@ int occ_waves(size_t lds, int) {
 void rtw_launch_render(const rtw_launch& L, void* stream, int variant, int grid) {
     hipStream_t st = (hipStream_t)stream;
     if (variant == 0) {
-        dim3 block(256);
-        dim3 g((L.W + 31) / 32, (L.n_rows + 7) / 8);
-        switch (pick_feat(rtw_feat_of(L) | RTW_F_ALL)) {
-        case RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR: hipLaunchKernelGGL(render_pixels_v0<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR>, g, block, 0, st, L); break;
-        case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR:
-            hipLaunchKernelGGL(render_pixels_v0<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>, g, block, 0, st, L);
-            break;
-        case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF:
-            hipLaunchKernelGGL(render_pixels_v0<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF>, g, block, 0, st, L);
-            break;
-        case RTW_F_ALL | RTW_F_PDF: hipLaunchKernelGGL(render_pixels_v0<RTW_F_ALL | RTW_F_PDF>, g, block, 0, st, L); break;
-        case RTW_F_ALL | RTW_F_TREE: hipLaunchKernelGGL(render_pixels_v0<RTW_F_ALL | RTW_F_TREE>, g, block, 0, st, L); break;
-        default: hipLaunchKernelGGL(render_pixels_v0<RTW_F_ALL>, g, block, 0, st, L); break;
-        }
+        const dim3 g((L.W + 31) / 32, (L.n_rows + 7) / 8);
+        rtw_with_class<false>(rtw_feat_of(L), [&](auto c) {
+            hipLaunchKernelGGL(render_pixels_v0<decltype(c)::value>, g, dim3(256), 0, st, L);
+        });
         return;
     }
-    const bool lds = L.n_nodes <= RTW_MEGA_LDS_NODES_MAX && L.use_lds;
-    const int w = (int)L.waves;
-    switch (pick_feat(rtw_feat_of(L))) {
-    case RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR:
-        lds ? launch_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR, true>(L, st, grid, w) : launch_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR, false>(L, st, grid, w);
-        break;
-    case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR:
-        lds ? launch_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR, true>(L, st, grid, w)
-            : launch_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR, false>(L, st, grid, w);
-        break;
-    case RTW_F_ALL | RTW_F_PDF:
-        lds ? launch_waves<RTW_F_ALL | RTW_F_PDF, true>(L, st, grid, w)
-            : launch_waves<RTW_F_ALL | RTW_F_PDF, false>(L, st, grid, w);
-        break;
-    case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF:
-        lds ? launch_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF, true>(L, st, grid, w)
-            : launch_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF, false>(L, st, grid, w);
-        break;
-    case 0u:
-        lds ? launch_waves<0u, true>(L, st, grid, w) : launch_waves<0u, false>(L, st, grid, w);
-        break;
-    case RTW_F_CHECKER:
-        lds ? launch_waves<RTW_F_CHECKER, true>(L, st, grid, w) : launch_waves<RTW_F_CHECKER, false>(L, st, grid, w);
-        break;
-    case RTW_F_ALL | RTW_F_TREE:
-        lds ? launch_waves<RTW_F_ALL | RTW_F_TREE, true>(L, st, grid, w)
-            : launch_waves<RTW_F_ALL | RTW_F_TREE, false>(L, st, grid, w);
-        break;
-    default:
-        lds ? launch_waves<RTW_F_ALL, true>(L, st, grid, w) : launch_waves<RTW_F_ALL, false>(L, st, grid, w);
-        break;
-    }
+    const bool lds = v1_lds(L.n_nodes, L.use_lds);
+    with_v1(rtw_feat_of(L), lds, [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds ? (size_t)L.n_nodes * 32 : 0, st, L);
+    });
 }
 
-int rtw_persistent_grid(uint32_t feat, uint32_t n_nodes, int waves, bool use_lds) {
+int rtw_persistent_grid(uint32_t feat, uint32_t n_nodes, bool use_lds) {
     int dev = 0, n_cu = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
     if (n_cu <= 0) n_cu = 256;
-    const bool lds = n_nodes <= RTW_MEGA_LDS_NODES_MAX && use_lds;
-    const size_t bytes = (size_t)n_nodes * 32;
-    int b;
-    switch (pick_feat(feat)) {
-    case RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR:
-        b = lds ? occ_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR, true>(bytes, waves) : occ_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR, false>(bytes, waves);
-        break;
-    case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR:
-        b = lds ? occ_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR, true>(bytes, waves)
-                : occ_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR, false>(bytes, waves);
-        break;
-    case RTW_F_ALL | RTW_F_PDF:
-        b = lds ? occ_waves<RTW_F_ALL | RTW_F_PDF, true>(bytes, waves) : occ_waves<RTW_F_ALL | RTW_F_PDF, false>(bytes, waves);
-        break;
-    case RTW_F_ALL | RTW_F_TREE | RTW_F_PDF:
-        b = lds ? occ_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF, true>(bytes, waves)
-                : occ_waves<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF, false>(bytes, waves);
-        break;
-    case 0u: b = lds ? occ_waves<0u, true>(bytes, waves) : occ_waves<0u, false>(bytes, waves); break;
-    case RTW_F_CHECKER:
-        b = lds ? occ_waves<RTW_F_CHECKER, true>(bytes, waves) : occ_waves<RTW_F_CHECKER, false>(bytes, waves);
-        break;
-    case RTW_F_ALL | RTW_F_TREE:
-        b = lds ? occ_waves<RTW_F_ALL | RTW_F_TREE, true>(bytes, waves)
-                : occ_waves<RTW_F_ALL | RTW_F_TREE, false>(bytes, waves);
-        break;
-    default: b = lds ? occ_waves<RTW_F_ALL, true>(bytes, waves) : occ_waves<RTW_F_ALL, false>(bytes, waves); break;
-    }
-    return n_cu * b;
+    const bool lds = v1_lds(n_nodes, use_lds);
+    int b = 0;
+    with_v1(feat, lds, [&](auto kernel) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kernel, 256, lds ? (size_t)n_nodes * 32 : 0) != hipSuccess)
+            b = 1;
+    });
+    return n_cu * (b < 1 ? 1 : b);
 }
 
 void rtw_launch_debug_rng(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t n, float* d_out, void* stream) {
@@ -526,21 +443,8 @@ void rtw_launch_debug_rng(uint64_t seed, uint32_t pixel, uint32_t sample, uint32
 }
 
 void rtw_launch_debug_sample(const rtw_launch& L, uint32_t pixel, uint32_t sample, float* d_out, void* stream) {
-    if (L.vattrs && L.n_lights)
-        hipLaunchKernelGGL(debug_sample_kernel<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>, dim3(1), dim3(64), 0, (hipStream_t)stream,
-                           L, pixel, sample, d_out);
-    else if (L.vattrs)
-        hipLaunchKernelGGL(debug_sample_kernel<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR>, dim3(1), dim3(64), 0, (hipStream_t)stream, L,
-                           pixel, sample, d_out);
-    else if (L.n_lights && (L.feat & RTW_F_TREE))
-        hipLaunchKernelGGL(debug_sample_kernel<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF>, dim3(1), dim3(64), 0, (hipStream_t)stream, L,
-                           pixel, sample, d_out);
-    else if (L.n_lights)
-        hipLaunchKernelGGL(debug_sample_kernel<RTW_F_ALL | RTW_F_PDF>, dim3(1), dim3(64), 0, (hipStream_t)stream, L, pixel,
+    rtw_with_class<false>(rtw_feat_of(L), [&](auto c) {
+        hipLaunchKernelGGL(debug_sample_kernel<decltype(c)::value>, dim3(1), dim3(64), 0, (hipStream_t)stream, L, pixel,
                            sample, d_out);
-    else if (L.feat & RTW_F_TREE)
-        hipLaunchKernelGGL(debug_sample_kernel<RTW_F_ALL | RTW_F_TREE>, dim3(1), dim3(64), 0, (hipStream_t)stream, L, pixel,
-                           sample, d_out);
-    else
-        hipLaunchKernelGGL(debug_sample_kernel<RTW_F_ALL>, dim3(1), dim3(64), 0, (hipStream_t)stream, L, pixel, sample, d_out);
+    });
 }

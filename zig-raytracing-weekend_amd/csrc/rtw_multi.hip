@@ -95,33 +95,20 @@ __global__ __launch_bounds__(256) void shard_rows_copy(float4* __restrict__ fram
 
 int ensure_buffers(rtw_multi* m, size_t tile_elems, size_t frame_elems) {
     const uint32_t n = (uint32_t)m->ctx.size();
-    if (m->tile_elems < tile_elems) {
-        for (uint32_t k = 0; k < n; k++) {
-            MHIP(hipSetDevice(m->dev[k]));
-            MHIP(hipStreamSynchronize(m->ctx[k]->stream));
-            if (m->tile[k]) (void)hipFree(m->tile[k]);
-            m->tile[k] = nullptr;
-        }
-        MHIP(hipSetDevice(m->dev[0]));
-        if (m->stacked) (void)hipFree(m->stacked);
-        m->stacked = nullptr;
+    if (m->tile_elems < tile_elems) {  // every device's tile and device 0's stack of them share one size
         m->tile_elems = 0;
+        size_t elems = 0;
+        MHIP(hipSetDevice(m->dev[0]));
+        MHIP(rtw_device_grow(&m->stacked, &elems, tile_elems, tile_elems * n * sizeof(float4), m->ctx[0]->stream));
         for (uint32_t k = 0; k < n; k++) {
             MHIP(hipSetDevice(m->dev[k]));
-            MHIP(hipMalloc(&m->tile[k], tile_elems * sizeof(float4)));
+            MHIP(rtw_device_grow(&m->tile[k], &elems, tile_elems, tile_elems * sizeof(float4), m->ctx[k]->stream));
         }
-        MHIP(hipSetDevice(m->dev[0]));
-        MHIP(hipMalloc(&m->stacked, tile_elems * n * sizeof(float4)));
         m->tile_elems = tile_elems;
     }
     if (frame_elems && m->frame_elems < frame_elems) {
         MHIP(hipSetDevice(m->dev[0]));
-        MHIP(hipStreamSynchronize(m->ctx[0]->stream));
-        if (m->frame) (void)hipFree(m->frame);
-        m->frame = nullptr;
-        m->frame_elems = 0;
-        MHIP(hipMalloc(&m->frame, frame_elems * sizeof(float4)));
-        m->frame_elems = frame_elems;
+        MHIP(rtw_device_grow(&m->frame, &m->frame_elems, frame_elems, frame_elems * sizeof(float4), m->ctx[0]->stream));
     }
     return RTW_OK;
 }
@@ -169,11 +156,8 @@ int multi_render(rtw_multi* m, const rtw_camera* cam, uint32_t rpb, uint32_t s0,
     const bool polled = rtw_polled(ctl);
     const uint64_t pixels = (uint64_t)W * H;
     uint32_t batch = spp_batch ? spp_batch : s1 - s0;
-    if (!spp_batch && polled) {  // the single-context auto batch of the largest shard
-        const uint64_t target = m->ctx[0]->variant == 2 ? m->ctx[0]->wf_max_paths : (64ull << 20);
-        const uint64_t b = target / std::max<uint64_t>(1, per);
-        batch = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(b, 1), s1 - s0);
-    }
+    // the single-context auto batch of the largest shard
+    if (!spp_batch && polled) batch = rtw_auto_batch(m->ctx[0], per, s1 - s0);
     int stop = RTW_OK;
     rtw_render_opts o{};
     o.flags = RTW_RENDER_NO_SYNC;
@@ -216,11 +200,22 @@ int multi_render(rtw_multi* m, const rtw_camera* cam, uint32_t rpb, uint32_t s0,
 
 int check_args(rtw_multi* m, const rtw_camera* cam, uint32_t rpb, uint32_t s0, uint32_t s1) {
     if (!m) return mfail(RTW_E_INVALID, "null rtw_multi");
-    if (!cam || cam->image_width == 0 || cam->image_height == 0) return mfail(RTW_E_INVALID, "camera not initialised");
-    if ((uint64_t)cam->image_width * cam->image_height > 0xFFFFFFFFull) return mfail(RTW_E_INVALID, "image too large");
+    if (!cam) return mfail(RTW_E_INVALID, "camera not initialised");
+    if (int rc = rtw_validate_cam(cam)) return rc;
     if ((rpb & ~RTW_ROWS_FLAGS) == 0) return mfail(RTW_E_INVALID, "rows_per_block == 0");
     if (s0 > s1) return mfail(RTW_E_INVALID, "bad sample range");
     return RTW_OK;
+}
+
+// a context's registrations, copied under its lock (rtw_scene_set_lights / rtw_scene_set_vertex_attrs write there)
+struct Registered {
+    std::vector<rtw_object> lights;
+    std::vector<uint32_t> quads;
+    std::vector<rtw_vertex_attr> attrs;
+};
+Registered registered(rtw_ctx* ctx) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    return {ctx->lights, ctx->vattr_quads, ctx->vattr_set};
 }
 
 }  // namespace
@@ -243,23 +238,21 @@ int rtw_multi_create(rtw_ctx* const* ctxs, uint32_t n, rtw_multi** out) {
                 return mfail(RTW_E_INVALID, "two contexts on one device (one context per device)");
             }
         // every device renders its rows of ONE estimator: the same registered lights, in the same order
-        {
-            const std::vector<rtw_object>&a = ctxs[0]->lights, &b = ctxs[k]->lights;
-            bool same = a.size() == b.size();
-            for (size_t i = 0; same && i < a.size(); i++) same = a[i].kind == b[i].kind && a[i].index == b[i].index;
-            if (!same) {
-                delete m;
-                return mfail(RTW_E_INVALID, "the contexts' light lists differ (rtw_scene_set_lights on each of them)");
-            }
+        const Registered a = registered(ctxs[0]), b = registered(ctxs[k]);
+        bool same = a.lights.size() == b.lights.size();
+        for (size_t i = 0; same && i < a.lights.size(); i++)
+            same = a.lights[i].kind == b.lights[i].kind && a.lights[i].index == b.lights[i].index;
+        if (!same) {
+            delete m;
+            return mfail(RTW_E_INVALID, "the contexts' light lists differ (rtw_scene_set_lights on each of them)");
         }
         // ... and the same vertex attributes
-        if (ctxs[0]->vattr_quads != ctxs[k]->vattr_quads ||
-            ctxs[0]->vattr_set.size() != ctxs[k]->vattr_set.size() ||
-            (!ctxs[0]->vattr_set.empty() &&
-             std::memcmp(ctxs[0]->vattr_set.data(), ctxs[k]->vattr_set.data(),
-                         ctxs[0]->vattr_set.size() * sizeof(rtw_vertex_attr)) != 0)) {
+        if (a.quads != b.quads || a.attrs.size() != b.attrs.size() ||
+            (!a.attrs.empty() &&
+             std::memcmp(a.attrs.data(), b.attrs.data(), a.attrs.size() * sizeof(rtw_vertex_attr)) != 0)) {
             delete m;
-            return mfail(RTW_E_INVALID, "the contexts' vertex attributes differ (rtw_scene_set_vertex_attrs on each of them)");
+            return mfail(RTW_E_INVALID,
+                         "the contexts' vertex attributes differ (rtw_scene_set_vertex_attrs on each of them)");
         }
         m->ctx.push_back(ctxs[k]);
         m->dev.push_back(ctxs[k]->device);
@@ -320,8 +313,7 @@ int rtw_render_multi_ex(rtw_multi* m, const rtw_camera* cam, uint32_t rpb, uint3
                         float* accum, const rtw_render_opts* opts) {
     if (int rc = check_args(m, cam, rpb, s0, s1)) return rc;
     if (!accum) return mfail(RTW_E_INVALID, "null accum");
-    if (opts && (opts->flags || opts->counters || opts->timing))
-        return mfail(RTW_E_INVALID, "host-buffer render: flags, counters and timing must be 0/NULL");
+    if (int rc = rtw_check_host_opts(opts)) return rc;
     if (s0 == s1) return RTW_OK;
     if (rtw_stop_requested(opts)) return mfail(RTW_E_CANCELLED, "cancelled");
     std::lock_guard<std::mutex> lock(m->mu);

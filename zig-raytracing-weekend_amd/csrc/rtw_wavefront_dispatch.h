@@ -397,12 +397,8 @@ uint32_t wf_class_waves(int n_cu) {
 #define RTW_F_TEXTURED (RTW_F_CHECKER | RTW_F_IMAGE | RTW_F_NOISE)
 #define RTW_F_MEDIA (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_LIGHT | RTW_F_CHECKER)
 uint32_t wf_pick_feat(uint32_t f) {
-    // vertex attributes registered (rtw_feat_of): their two instantiations, on top of every feature and the
-    // instance trees (a scene without a tree runs them too: inst_hit_t falls back to the member loop)
-    if (f & RTW_F_ATTR) return RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR | (f & RTW_F_PDF);
-    // lights registered (rtw_feat_of): the mixture-density instantiations, on top of every feature
-    if (f & RTW_F_PDF) return (f & RTW_F_TREE) ? (RTW_F_ALL | RTW_F_TREE | RTW_F_PDF) : (RTW_F_ALL | RTW_F_PDF);
-    if (f & RTW_F_TREE) return RTW_F_ALL | RTW_F_TREE;  // instance trees (inst_tree_t): their own instantiation
+    // registered vertex attributes or lights, instance trees: their own instantiations (rtw_internal.h)
+    if (const uint32_t p = rtw_feat_prefix(f)) return p;
     if ((f & ~RTW_F_CHECKER) == 0) return f ? RTW_F_CHECKER : 0u;
     if ((f & RTW_F_GEOM) && (f & ~RTW_F_OBJECTS) == 0) return RTW_F_OBJECTS;
     if ((f & ~RTW_F_TEXTURED) == 0) return RTW_F_TEXTURED;
