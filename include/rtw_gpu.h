@@ -233,7 +233,9 @@ typedef struct rtw_camera_params {
 
 typedef struct rtw_camera {
     uint32_t image_width, image_height, size, samples_per_pixel, max_depth;
-    uint32_t background_mode, pixel_offset, _pad;
+    uint32_t background_mode, pixel_offset;
+    uint32_t strata;           /* stratified pixel samples (rtw_camera_set_strata); 0 from rtw_camera_init. The
+                                * word was padding: the struct and RTW_ABI_VERSION are those of ABI 8 */
     float center[3], pixel00_loc[3], pixel_delta_u[3], pixel_delta_v[3];
     float u[3], v[3], w[3];
     float defocus_disk_u[3], defocus_disk_v[3];
@@ -288,6 +290,20 @@ int rtw_device_count(int* out);
 
 /* Camera.init (src/camera.zig:118-154). Host-only arithmetic; shared by every caller. */
 int rtw_camera_init(const rtw_camera_params* params, rtw_camera* out);
+
+/* Stratified pixel samples (the jittering of "The Rest of Your Life"; detected by this symbol's presence).
+ * With strata = n > 1, sample s of a pixel -- s the absolute 0-based index, whatever call, batch, shard or
+ * GPU renders it -- is jittered inside cell k = s mod n^2 of an n x n grid over the pixel: si = k mod n along
+ * pixel_delta_u, sj = k div n along pixel_delta_v (row order), and with inv = 1 / (float)n
+ *     px = ((si + rx) * inv) - 0.5,  py = ((sj + ry) * inv) - 0.5     (fp32, each operation rounded)
+ * where rx, ry are the two draws the plain jitter -0.5 + r takes, in its order: no draw is added, and every
+ * later draw of the path keeps its place.  n^2 consecutive samples from a multiple of n^2 visit every cell
+ * once; samples past the last full pass are a prefix of the next one.  0 and 1 are off: the plain jitter,
+ * bit for bit.  A cell is closed on both sides (px can round up to +0.5).
+ * rtw_camera_set_strata stores n; n > RTW_MAX_STRATA or a null camera: RTW_E_INVALID, the camera left as
+ * it was.  Every render entry point and rtw_debug_sample refuse a camera whose strata exceeds the maximum. */
+#define RTW_MAX_STRATA 256
+int rtw_camera_set_strata(rtw_camera* cam, uint32_t n);
 
 /* Builds the BVH (bvh_mode) on the host, flattens it to 32-byte depth-first
  * nodes with skip links, and uploads nodes / materials / textures / images /
@@ -619,6 +635,13 @@ int rtw_scene_instance_nodes(rtw_ctx* ctx, uint32_t instance, void* out, uint32_
 int rtw_debug_rng(rtw_ctx* ctx, uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t n, float* out);
 int rtw_debug_sample(rtw_ctx* ctx, const rtw_camera* cam, uint64_t seed, uint32_t pixel, uint32_t sample,
                      float out[3]);
+/* Host-only (no context): Camera.getRay -- get_ray, the code every kernel runs -- for n (pixel, sample) pairs
+ * of the render with this seed: pixel pixels[i] (y * image_width + x, the camera's pixel_offset applied as a
+ * render applies it), absolute sample index samples[i].  origin[3 i ..], dir[3 i ..], time[i], and
+ * jitter[2 i ..] = (px, py), the offsets inside the pixel (see rtw_camera_set_strata).  Any output may be
+ * NULL.  A pixel out of range or strata > RTW_MAX_STRATA: RTW_E_INVALID. */
+int rtw_debug_camera_ray(const rtw_camera* cam, uint64_t seed, uint32_t n, const uint32_t* pixels,
+                         const uint32_t* samples, float* origin, float* dir, float* time, float* jitter);
 /* ABI 6, host-only: the walk's sphere fast-reject (sphere_may_hit, the same fp32 operations as the
  * device) and Sphere.hit's exact accept (objects.zig:127-136, tmin = 0.001) for n sphere tests given
  * a = lengthSquared(d), half_b = dot(oc, d), c = lengthSquared(oc) - r*r and closest: the test suite

@@ -35,6 +35,7 @@ RTW_DEAL_RUNS, RTW_DEAL_TAIL, RTW_DEAL_SMALL, RTW_DEAL_ITERS, RTW_DEAL_SINGLES16
 RTW_DEAL_SMALL_SORT, RTW_DEAL_ALL = 128, 187
 RTW_DEVICE_CPU = -1
 RTW_MAX_LIGHTS = 16
+RTW_MAX_STRATA = 256  # rtw_camera.strata: n x n jitter cells per pixel, n^2 <= 2^16
 
 # numpy record layouts == the C structs (asserted against sizeof in tests)
 SPHERE_DT = np.dtype([("center1", "<f4", 3), ("radius", "<f4"), ("center2", "<f4", 3), ("is_moving", "<u4"),
@@ -111,7 +112,7 @@ class RtwCameraParams(C.Structure):
 class RtwCamera(C.Structure):
     _fields_ = [("image_width", C.c_uint32), ("image_height", C.c_uint32), ("size", C.c_uint32),
                 ("samples_per_pixel", C.c_uint32), ("max_depth", C.c_uint32), ("background_mode", C.c_uint32),
-                ("pixel_offset", C.c_uint32), ("_pad", C.c_uint32),
+                ("pixel_offset", C.c_uint32), ("strata", C.c_uint32),
                 ("center", F3), ("pixel00_loc", F3), ("pixel_delta_u", F3), ("pixel_delta_v", F3),
                 ("u", F3), ("v", F3), ("w", F3), ("defocus_disk_u", F3), ("defocus_disk_v", F3),
                 ("defocus_angle", C.c_float), ("background", F3)]
@@ -185,6 +186,9 @@ SIGNATURES = {
     "rtw_last_error": (C.c_char_p, []),
     "rtw_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "rtw_camera_init": (C.c_int, [C.POINTER(RtwCameraParams), C.POINTER(RtwCamera)]),
+    "rtw_camera_set_strata": (C.c_int, [C.POINTER(RtwCamera), C.c_uint32]),
+    "rtw_debug_camera_ray": (C.c_int, [C.POINTER(RtwCamera), C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtw_scene_create": (C.c_int, [C.POINTER(RtwSceneDesc), C.c_int, C.POINTER(C.c_void_p)]),
     "rtw_scene_destroy": (None, [C.c_void_p]),
     "rtw_tuning_defaults": (None, [C.POINTER(RtwTuning)]),

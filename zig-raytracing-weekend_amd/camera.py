@@ -12,7 +12,7 @@ pixel chunk and the whole sample range; the per-sample loop runs on the GPU.
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, field
+from dataclasses import InitVar, dataclass, field
 from typing import Callable, Optional
 
 import numpy as np
@@ -71,7 +71,10 @@ class SharedStateImageWriter:
 class Camera:
     """camera.zig:69-91 (defaults are the reference's), plus the two knobs the
     reference hard-codes: background_mode (gradient = the commented Book-1 sky,
-    camera.zig:204-206) and pixel_offset (the +1 of camera.zig:100-101)."""
+    camera.zig:204-206) and pixel_offset (the +1 of camera.zig:100-101); and strata, the stratified
+    pixel samples of "The Rest of Your Life": sample s of a pixel is jittered inside cell s mod n^2 of an
+    n x n grid over the pixel (row order; s the absolute sample index, so any split of the samples into
+    calls renders the same image).  0 and 1 are off; at most RTW_MAX_STRATA."""
     aspect_ratio: float = 16.0 / 9.0
     image_width: int = 800
     image_height: int = 0
@@ -87,6 +90,12 @@ class Camera:
     focus_dist: float = 10.0
     pixel_offset: int = 1
     derived: Optional[_abi.RtwCamera] = field(default=None, repr=False)
+    # strata is ours, not one of camera.zig's fields: an init-only variable kept as a plain attribute, so that
+    # dataclasses.fields(camera) stays the reference's Camera (callers build the oracle's camera from it)
+    strata: InitVar[int] = 0
+
+    def __post_init__(self, strata: int = 0):
+        self.strata = strata
 
     def params(self) -> _abi.RtwCameraParams:
         p = _abi.RtwCameraParams()
@@ -110,6 +119,8 @@ class Camera:
         """Camera.init (camera.zig:118-154) via rtw_camera_init."""
         c = _abi.RtwCamera()
         _abi.check(_abi.lib().rtw_camera_init(C.byref(self.params()), C.byref(c)), "rtw_camera_init")
+        if self.strata:  # (0 is what rtw_camera_init leaves)
+            _abi.check(_abi.lib().rtw_camera_set_strata(C.byref(c), self.strata), "rtw_camera_set_strata")
         self.derived = c
         if self.image_height == 0:
             self.image_height = c.image_height

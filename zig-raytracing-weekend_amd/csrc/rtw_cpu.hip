@@ -78,6 +78,47 @@ int rtw_cpu_render(const rtw_launch& L, uint32_t begin, uint32_t end, float* out
     return stopped ? RTW_E_CANCELLED : RTW_OK;
 }
 
+// Host-only test hook (include/rtw_gpu.h), and the symbol a caller detects stratified pixel samples by: get_ray --
+// the device's code, the same fp32 operations, the path's own RNG stream -- for n (pixel, sample) pairs
+namespace {
+Ray debug_get_ray(const rtw_launch& L, uint32_t pixel, uint32_t s, float* jit) {
+    rtw_rng rng;
+    rng.s = rtw_mix64(L.key0 ^ (((uint64_t)pixel << 32) | (uint64_t)s));  // sample_radiance's stream
+    return get_ray(L, pixel % L.W + L.pixel_offset, pixel / L.W + L.pixel_offset, stratum_of(L.strata, s), rng, jit);
+}
+}  // namespace
+extern "C" int rtw_debug_camera_ray(const rtw_camera* cam, uint64_t seed, uint32_t n, const uint32_t* pixels,
+                                    const uint32_t* samples, float* origin, float* dir, float* time, float* jitter) {
+    if (int rc = rtw_validate_cam(cam)) return rc;
+    if (n && (!pixels || !samples)) {
+        rtw_set_error("rtw_debug_camera_ray: null pixels / samples");
+        return RTW_E_INVALID;
+    }
+    rtw_launch L{};
+    rtw_launch_camera(L, cam, seed);
+    for (uint32_t i = 0; i < n; i++) {
+        if (pixels[i] >= cam->size) {
+            char msg[96];
+            std::snprintf(msg, sizeof msg, "rtw_debug_camera_ray: pair %u: pixel %u out of range", i, pixels[i]);
+            rtw_set_error(msg);
+            return RTW_E_INVALID;
+        }
+        float jit[2];
+        const Ray r = debug_get_ray(L, pixels[i], samples[i], jit);
+        const float o[3] = {r.o.x, r.o.y, r.o.z}, d[3] = {r.d.x, r.d.y, r.d.z};
+        for (int k = 0; k < 3; k++) {
+            if (origin) origin[3 * (size_t)i + k] = o[k];
+            if (dir) dir[3 * (size_t)i + k] = d[k];
+        }
+        if (time) time[i] = r.time;
+        if (jitter) {
+            jitter[2 * (size_t)i] = jit[0];
+            jitter[2 * (size_t)i + 1] = jit[1];
+        }
+    }
+    return RTW_OK;
+}
+
 // ABI 6 test hook (include/rtw_gpu.h): the walk's sphere fast-reject against Sphere.hit's exact accept, on
 // the host -- sphere_may_hit is the device's code (rtw_device.h), the same fp32 operations
 extern "C" int rtw_debug_sphere_filter(uint32_t n, const float* a, const float* half_b, const float* c,

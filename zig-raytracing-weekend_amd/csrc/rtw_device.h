@@ -195,12 +195,41 @@ struct Ray {
     float time;
 };
 
-// Camera.getRay (camera.zig:156-180)
-RTW_DHD Ray get_ray(const rtw_launch& L, uint32_t i, uint32_t j, rtw_rng& rng) {
+// Stratified pixel samples (rtw_camera.strata = n, DESIGN.md §Stratified pixel samples): sample s of a pixel
+// is jittered inside cell k = s mod n^2 of an n x n grid over the pixel, si = k mod n along du and sj = k div n
+// along dv (row order, s_j outer), with inv = fl(1 / fl(n)):
+//   px = fl(fl(fl(fl(si) + rx) * inv) - 0.5)      py = fl(fl(fl(fl(sj) + ry) * inv) - 0.5)
+// rx, ry: the two draws of the plain jitter, in its order.  n <= 1 is the cell (0, 0) with inv = 1, and
+// fl(fl(0 + r) * 1) - 0.5 is -0.5 + r bit for bit (0 + r and r * 1 are exact for r in [0, 1), and fp32 addition
+// commutes).  The stratum depends on the absolute sample index alone, never on how [0, spp) is cut into calls.
+struct Stratum {
+    float si, sj, inv;
+};
+RTW_DHD Stratum stratum_of(uint32_t n, uint32_t s) {
+    Stratum c;
+    c.si = c.sj = 0.0f;
+    c.inv = 1.0f;
+    if (n > 1) {  // n <= RTW_MAX_STRATA = 256: n * n <= 2^16, si and sj < 256 are exact in fp32
+        const uint32_t k = s % (n * n), j = k / n;
+        c.si = (float)(k - j * n);
+        c.sj = (float)j;
+        c.inv = 1.0f / (float)n;  // one correctly rounded division
+    }
+    return c;
+}
+// (built without FMA contraction: a product, then a sum)
+RTW_DHD float stratum_jitter(float cell, float r, float inv) { return ((cell + r) * inv) - 0.5f; }
+
+// Camera.getRay (camera.zig:156-180); c: the sample's stratum (stratum_of), jit (out, may be null): (px, py)
+RTW_DHD Ray get_ray(const rtw_launch& L, uint32_t i, uint32_t j, const Stratum& c, rtw_rng& rng, float* jit = nullptr) {
     const f3 du = ld3(L.du), dv = ld3(L.dv);
     f3 pixel_center = (ld3(L.pixel00) + du * splat((float)i)) + dv * splat((float)j);
-    float px = -0.5f + rnd(rng);
-    float py = -0.5f + rnd(rng);
+    float px = stratum_jitter(c.si, rnd(rng), c.inv);
+    float py = stratum_jitter(c.sj, rnd(rng), c.inv);
+    if (jit) {
+        jit[0] = px;
+        jit[1] = py;
+    }
     f3 pixel_sample = pixel_center + (splat(px) * du + splat(py) * dv);
     f3 origin;
     if (L.defocus_angle <= 0) {
@@ -219,6 +248,10 @@ RTW_DHD Ray get_ray(const rtw_launch& L, uint32_t i, uint32_t j, rtw_rng& rng) {
     r.d = pixel_sample - origin;
     r.time = rnd(rng);
     return r;
+}
+// sample s (absolute index) of pixel (i, j): the stratum per call, two integer divisions when strata are on
+RTW_DHD Ray get_ray(const rtw_launch& L, uint32_t i, uint32_t j, uint32_t s, rtw_rng& rng) {
+    return get_ray(L, i, j, stratum_of(L.strata, s), rng);
 }
 
 // Texture.value (textures.zig:22-123)
@@ -1590,14 +1623,14 @@ RTW_DHD void seq_reject(rtw_rng& rng, float (&out)[D]) {
 
 // Camera.getRay for every lane of the wave (`active` lanes get a ray): the same
 // draws in the same order as get_ray, the disk's rejection loop outside the
-// per-lane branch (one loop for the wave).
-RTW_DHD Ray get_ray_wave(const rtw_launch& L, bool active, uint32_t i, uint32_t j, rtw_rng& rng) {
+// per-lane branch (one loop for the wave); c: the sample's stratum, the same for the whole wave.
+RTW_DHD Ray get_ray_wave(const rtw_launch& L, bool active, uint32_t i, uint32_t j, const Stratum& c, rtw_rng& rng) {
     const f3 du = ld3(L.du), dv = ld3(L.dv);
     f3 pixel_sample = mk(0, 0, 0);
     if (active) {
         const f3 pixel_center = (ld3(L.pixel00) + du * splat((float)i)) + dv * splat((float)j);
-        const float px = -0.5f + rnd(rng);
-        const float py = -0.5f + rnd(rng);
+        const float px = stratum_jitter(c.si, rnd(rng), c.inv);
+        const float py = stratum_jitter(c.sj, rnd(rng), c.inv);
         pixel_sample = pixel_center + (splat(px) * du + splat(py) * dv);
     }
     f3 origin = ld3(L.center);
@@ -1619,7 +1652,7 @@ __host__ __device__ f3 sample_radiance(const float4* __restrict__ nodes, const r
                               uint32_t y, uint32_t s, Counters& cnt) {
     rtw_rng rng;
     rng.s = rtw_mix64(L.key0 ^ (((uint64_t)pixel << 32) | (uint64_t)s));
-    Ray r = get_ray(L, x, y, rng);
+    Ray r = get_ray(L, x, y, s, rng);
     f3 acc = mk(0, 0, 0);
     f3 thr = mk(1, 1, 1);
     for (uint32_t depth = L.max_depth; depth > 0; depth--) {

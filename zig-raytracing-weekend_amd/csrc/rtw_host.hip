@@ -581,6 +581,14 @@ int rtw_camera_init(const rtw_camera_params* p, rtw_camera* c) {
     return RTW_OK;
 }
 
+// Stratified pixel samples: n x n jitter cells per pixel (rtw_device.h stratum_of); 0 and 1 are off
+int rtw_camera_set_strata(rtw_camera* cam, uint32_t n) {
+    if (!cam) return fail(RTW_E_INVALID, "rtw_camera_set_strata: null camera");
+    if (n > RTW_MAX_STRATA) return fail(RTW_E_INVALID, "rtw_camera_set_strata: strata exceeds RTW_MAX_STRATA (256)");
+    cam->strata = n;
+    return RTW_OK;
+}
+
 void rtw_tuning_defaults(rtw_tuning* t) {
     if (!t) return;
     std::memset(t, 0, sizeof *t);
@@ -952,6 +960,23 @@ namespace {
 
 rtw_launch make_launch(const rtw_ctx* ctx, const rtw_camera* c, uint64_t seed) {
     rtw_launch L = ctx->base;
+    rtw_launch_camera(L, c, seed);
+    if (L.fast_box) {
+        // the box pad covers ray origins with |o| <= 7 * extent (rtw_bvh.hip): primary
+        // origins are the camera centre + the defocus disk; secondary ones lie in the scene
+        float o = 0;
+        for (int k = 0; k < 3; k++)
+            o = std::max(o, std::fabs(c->center[k]) + std::fabs(c->defocus_disk_u[k]) +
+                                std::fabs(c->defocus_disk_v[k]));
+        if (!(o <= 7.0f * ctx->extent)) L.fast_box = 0;
+    }
+    return L;
+}
+
+}  // namespace
+
+// the camera's part of a launch, and the render-domain key (make_launch; rtw_debug_camera_ray, which has no context)
+void rtw_launch_camera(rtw_launch& L, const rtw_camera* c, uint64_t seed) {
     for (int k = 0; k < 3; k++) {
         L.center[k] = c->center[k];
         L.pixel00[k] = c->pixel00_loc[k];
@@ -967,20 +992,9 @@ rtw_launch make_launch(const rtw_ctx* ctx, const rtw_camera* c, uint64_t seed) {
     L.max_depth = c->max_depth;
     L.bg_mode = c->background_mode;
     L.pixel_offset = c->pixel_offset;
+    L.strata = c->strata;
     L.key0 = rtw_mix64(seed);
-    if (L.fast_box) {
-        // the box pad covers ray origins with |o| <= 7 * extent (rtw_bvh.hip): primary
-        // origins are the camera centre + the defocus disk; secondary ones lie in the scene
-        float o = 0;
-        for (int k = 0; k < 3; k++)
-            o = std::max(o, std::fabs(c->center[k]) + std::fabs(c->defocus_disk_u[k]) +
-                                std::fabs(c->defocus_disk_v[k]));
-        if (!(o <= 7.0f * ctx->extent)) L.fast_box = 0;
-    }
-    return L;
 }
-
-}  // namespace
 
 uint32_t rtw_auto_batch(const rtw_ctx* ctx, uint64_t pixels, uint32_t spp) {
     // ~64M samples per launch (the wavefront: its batch capacity): long enough to
@@ -996,6 +1010,7 @@ int rtw_validate_cam(const rtw_camera* cam) {
     if (!cam) return fail(RTW_E_INVALID, "null camera");
     if (cam->image_width == 0 || cam->image_height == 0) return fail(RTW_E_INVALID, "camera not initialised");
     if ((uint64_t)cam->image_width * cam->image_height > 0xFFFFFFFFull) return fail(RTW_E_INVALID, "image too large");
+    if (cam->strata > RTW_MAX_STRATA) return fail(RTW_E_INVALID, "camera: strata exceeds RTW_MAX_STRATA (256)");
     return RTW_OK;
 }
 

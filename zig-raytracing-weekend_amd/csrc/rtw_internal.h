@@ -87,7 +87,7 @@ struct rtw_launch {
     uint32_t wf_clds : 8;        // wavefront trace: stage the compact nodes (all orders) in LDS when they fit
     uint32_t wf_fuse : 8;        // with the compact LDS stage: one gen+trace+shade kernel per iteration,
                                  // bit 1: the tail walks the LDS stage too (bits 0 .. 2 of rtw_tuning.fuse)
-    uint32_t _spare;
+    uint32_t strata;             // rtw_camera.strata: n x n jitter cells per pixel (0 / 1: off; rtw_device.h stratum_of)
     uint32_t perlin_lds;         // fused step with the node array in LDS: Perlin tables staged in LDS too
     uint32_t mat_lds;            // compact-LDS fused step: bytes of the material array staged in LDS (0: off)
     uint32_t shade_lds;          // node-LDS kernels: bytes of materials | textures | image records (contiguous
@@ -192,10 +192,12 @@ int rtw_persistent_grid(uint32_t feat, uint32_t n_nodes, bool use_lds);
 void rtw_launch_render(const rtw_launch& L, void* stream, int variant, int grid);
 void rtw_set_error(const char* msg);  // the thread's rtw_last_error() message (rtw_host.hip)
 // Checks the render entry points of rtw_host.hip and rtw_multi.hip share (they set the error message): the camera
-// is non-null and initialised and its image addressable; the host-buffer entry points' options hold stop / progress
+// is non-null and initialised, its image addressable and its strata within RTW_MAX_STRATA; the host-buffer entry points' options hold stop / progress
 // and spp_batch only.  And the automatic batch: samples per launch of `pixels` pixels, at most spp.
 struct rtw_ctx;
 int rtw_validate_cam(const rtw_camera* cam);
+struct rtw_launch;
+void rtw_launch_camera(rtw_launch& L, const rtw_camera* c, uint64_t seed);  // the camera's fields and the key
 int rtw_check_host_opts(const rtw_render_opts* o);
 uint32_t rtw_auto_batch(const rtw_ctx* ctx, uint64_t pixels, uint32_t spp);
 // A device buffer that grows on demand: replaces *buf (after the work on `s` that may still use it) by a fresh

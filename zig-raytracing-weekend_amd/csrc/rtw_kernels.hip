@@ -182,8 +182,12 @@ __global__ __launch_bounds__(256, WAVES) void render_persistent_v1(rtw_launch L)
                 rng.s = rtw_mix64(L.key0 ^ (((uint64_t)pixel << 32) | (uint64_t)s));
                 const f3 du = ld3(L.du), dv = ld3(L.dv);
                 const f3 pixel_center = (ld3(L.pixel00) + du * splat((float)px)) + dv * splat((float)py);
-                const float jx = -0.5f + rnd(rng);
-                const float jy = -0.5f + rnd(rng);
+                // the sample's stratum, per lane (every lane is at its own s): stratum_of's two integer
+                // divisions are the compiler's u32 expansion, exact for every s, n^2 and n; strata off
+                // (a uniform branch inside it) divides nothing
+                const Stratum sc = stratum_of(L.strata, s);
+                const float jx = stratum_jitter(sc.si, rnd(rng), sc.inv);
+                const float jy = stratum_jitter(sc.sj, rnd(rng), sc.inv);
                 pixel_sample = pixel_center + (splat(jx) * du + splat(jy) * dv);
             }
             float dsk[2] = {0.0f, 0.0f};
@@ -356,7 +360,7 @@ __global__ void debug_sample_kernel(rtw_launch L, uint32_t pixel, uint32_t sampl
     // replay the path to run the filter check on every bounce ray
     rtw_rng rng;
     rng.s = rtw_mix64(L.key0 ^ (((uint64_t)pixel << 32) | (uint64_t)sample));
-    Ray r = get_ray(L, x + L.pixel_offset, y + L.pixel_offset, rng);
+    Ray r = get_ray(L, x + L.pixel_offset, y + L.pixel_offset, sample, rng);
     f3 acc = mk(0, 0, 0), thr = mk(1, 1, 1);
     int bounce = 0;
     for (uint32_t depth = L.max_depth; depth > 0; depth--, bounce++) {

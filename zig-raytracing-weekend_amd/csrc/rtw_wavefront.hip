@@ -571,19 +571,34 @@ __device__ __forceinline__ void wf_store_path(const rtw_wf_set& O, uint32_t out,
 template <uint32_t FEAT>
 __device__ __forceinline__ bool wf_camera(const rtw_launch& L, const rtw_wf& W, bool got, uint32_t slot, Ray& r,
                                           rtw_rng& rng) {
+    // Every caller's slot comes from WfIter::get at iteration 0: slot0 | lane with slot0 = c << 6 wave-uniform (the
+    // static deal's wf_chunk0, the dynamic deal's runs and its single chunks alike), so the wave holds exactly one
+    // chunk -- one sample of one tile.  The compiler cannot prove slot >> 6 uniform, hence the readfirstlane (any
+    // active lane holds the same chunk): the chunk's tile and sample (wf_path) and the sample's stratum (rtw_device.h
+    // stratum_of) are computed once per chunk in scalar registers, no integer division per lane.
     uint32_t s_local = 0, q = 0, pixel = 0, out_idx, x = 0, y = 0;
     bool live = false;
     if (got) {
-        wf_path(W, slot, s_local, q);
+        wf_path(W, (__builtin_amdgcn_readfirstlane(slot >> 6) << 6) | (slot & 63u), s_local, q);
+        s_local = __builtin_amdgcn_readfirstlane(s_local);
         live = wf_pixel(L, W, q, pixel, out_idx, x, y) && L.max_depth > 0;
     }
     rng.s = live ? rtw_mix64(L.key0 ^ (((uint64_t)pixel << 32) | (uint64_t)(L.s0 + s_local))) : 0ull;
+    Stratum sc;
+    sc.si = sc.sj = 0.0f;
+    sc.inv = 1.0f;
+    if (L.strata > 1u) {  // strata off: a uniform branch (a kernel argument) around all of it
+        const Stratum u = stratum_of(L.strata, L.s0 + s_local);
+        sc.si = ubits(__builtin_amdgcn_readfirstlane(fbits(u.si)));
+        sc.sj = ubits(__builtin_amdgcn_readfirstlane(fbits(u.sj)));
+        sc.inv = ubits(__builtin_amdgcn_readfirstlane(fbits(u.inv)));
+    }
     r.o = r.d = mk(0, 0, 0);
     r.time = 0;
     if constexpr ((FEAT & (RTW_F_GEOM | RTW_F_MEDIUM)) == 0) {
-        r = get_ray_wave(L, live, x + L.pixel_offset, y + L.pixel_offset, rng);
+        r = get_ray_wave(L, live, x + L.pixel_offset, y + L.pixel_offset, sc, rng);
     } else {
-        if (live) r = get_ray(L, x + L.pixel_offset, y + L.pixel_offset, rng);
+        if (live) r = get_ray(L, x + L.pixel_offset, y + L.pixel_offset, sc, rng);
     }
     return live;
 }
