@@ -621,6 +621,74 @@ int rtw_scene_set_vertex_attrs(rtw_ctx* ctx, const uint32_t* quads, const rtw_ve
 /* Copies the registered entries, normals normalised (either output may be NULL; at most cap are written). */
 int rtw_scene_vertex_attrs_get(rtw_ctx* ctx, uint32_t* quads, rtw_vertex_attr* attrs, uint32_t cap, uint32_t* n_out);
 
+/* ---------------------------------------------------------------------------
+ * Denoised previews: first-hit guide buffers and an edge-avoiding a-trous filter (Dammertz et al. 2010) over the
+ * accumulator, for the handful of samples per pixel an interactive viewer shows.  A caller detects the capability
+ * by the presence of these symbols (the ABI version and every struct are those of ABI 8).  Kernels of their own:
+ * no render changes by a bit.  DESIGN.md §Denoised previews.
+ *
+ * Guides.  One deterministic ray per pixel: from cam->center through the pixel centre (pixel_offset applied as a
+ * render applies it), no jitter, no defocus disk, time 0, no RNG draw -- so no seed.  It is traced by the walk and
+ * the hit record every render uses, except that it sees through ConstantMedium (smoke is noise to filter, not an
+ * edge).  Both outputs are float4[W*H] in image order:
+ *   hit:   normal_depth = (the record's normal -- the shading normal where vertex attributes are registered --
+ *          turned towards the ray, depth = t * length(ray direction) > 0);  albedo.rgb = the texture's value at the
+ *          hit (Lambertian, Isotropic), the metal's albedo, (1, 1, 1) for a dielectric, the emit texture's value
+ *          for a DiffuseLight;  albedo.w = 1
+ *   miss:  normal_depth = 0 (a hit is depth > 0);  albedo.rgb = the background seen by the ray;  albedo.w = 0
+ * The same function runs on the GPU and on a host context: the two agree bit for bit.  Out of scope: guides
+ * through glass or mirrors (first hit only) and guides under defocus.
+ * rtw_render_guides: host buffers, GPU and host contexts.  rtw_render_guides_device: device buffers of a GPU
+ * context (a host context is refused), enqueued on `stream` (NULL: the context's); flags: RTW_RENDER_NO_SYNC.
+ *
+ * Filter.  Over the accumulator's mean radiance, all in fp32, every operation rounded singly (nothing contracted),
+ * one function for the host and the device, so they agree bit for bit:
+ *   pre-pass   c = rgb * (1 / w);  with RTW_DENOISE_DEMODULATE  c = c / max(albedo, 2^-8) per channel
+ *   pass i     (i = 0 .. passes - 1, spacing s = 2^i)  for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), the tap
+ *              q = p + s (dx, dy) is skipped if it is off the image, if its colour is not finite or if its hit
+ *              state (depth > 0) differs from the centre's; otherwise
+ *                x = ((|dc|^2 kc + |dn|^2 kn) + dz^2 kz),  |v|^2 = (v.x v.x + v.y v.y) + v.z v.z
+ *                kc = 1 / (sc sc), sc = sigma_color 2^-i  (term off -- 0 -- for the whole pixel if the centre colour
+ *                     is not finite);  kn = 1 / (sigma_normal sigma_normal);
+ *                kz = 1 / ((sigma_depth sigma_depth) (z_p z_p)) for a hit centre, else off;  a term whose sigma is 0
+ *                     is off
+ *                weight = (h[dx] h[dy]) e(x),  h = {1/16, 1/4, 3/8, 1/4, 1/16},  e(x) = exp(-x) (rtw_libm.h
+ *                     rtw_expneg: relative error below 2^-20, e(0) = 1, 0 above 87)
+ *              out = (sum of weight c_q) / (sum of weight), both sums in tap order; if the sum of weights is 0 the
+ *              pixel keeps its input.  A finite centre contributes 9/64, so its sum cannot vanish.
+ *   last pass  with DEMODULATE  c = c * max(albedo, 2^-8);  out.rgb = c * w, out.w = w: the accumulator's form, so
+ *              rtw_texture_from_accum*, the encoders and the checkpoints work on the result unchanged.
+ * A NaN / infinite pixel and a pixel with w = 0 are filled from their neighbours (the latter comes out 0: c * 0).
+ * out may alias accum; albedo may be NULL without DEMODULATE.  The two intermediate images belong to the context
+ * and grow on demand; the calls take the context lock as renders do.  RTW_E_INVALID with a message, out untouched:
+ * passes outside 1 .. RTW_DENOISE_MAX_PASSES, a negative or non-finite sigma, unknown flag bits, width * height == 0
+ * (or beyond 2^32 - 1), a null required pointer, rtw_denoise_device on a host context.  Out of scope: variance-guided
+ * or temporal filtering, a sharded multi-GPU filter (filter device 0's gathered frame), a pixel sub-range.
+ * ------------------------------------------------------------------------- */
+#define RTW_DENOISE_MAX_PASSES 8
+enum { RTW_DENOISE_DEMODULATE = 1u };
+typedef struct rtw_denoise_params {      /* 32 bytes */
+    uint32_t passes;                     /* 1..8; pass i taps at spacing 2^i */
+    uint32_t flags;                      /* RTW_DENOISE_* */
+    float sigma_color;                   /* pass i uses sigma_color * 2^-i; 0 = term off */
+    float sigma_normal, sigma_depth;     /* depth relative to the centre's; 0 = term off */
+    float _pad[3];
+} rtw_denoise_params;
+/* The shipped parameters: the winner of the grid search recorded in profiles/denoise/defaults.json. */
+void rtw_denoise_defaults(rtw_denoise_params* p);
+int rtw_render_guides(rtw_ctx* ctx, const rtw_camera* cam, float* albedo, float* normal_depth);
+int rtw_render_guides_device(rtw_ctx* ctx, const rtw_camera* cam, float* d_albedo, float* d_normal_depth,
+                             void* stream, uint32_t flags);
+/* Host buffers; GPU contexts (staged through the device: the device form is the fast path) and host contexts. */
+int rtw_denoise(rtw_ctx* ctx, uint32_t width, uint32_t height, const float* accum, const float* albedo,
+                const float* normal_depth, const rtw_denoise_params* params, float* out);
+/* Device buffers of a GPU context, enqueued on `stream` (NULL: the context's); flags: RTW_RENDER_NO_SYNC. */
+int rtw_denoise_device(rtw_ctx* ctx, uint32_t width, uint32_t height, const float* d_accum, const float* d_albedo,
+                       const float* d_normal_depth, const rtw_denoise_params* params, float* d_out, void* stream,
+                       uint32_t flags);
+/* Host-only: out[i] = e(x[i]) = exp(-x[i]), the filter's edge-stopping function (rtw_expneg, the device's code). */
+int rtw_debug_expneg(uint32_t n, const float* x, float* out);
+
 /* Copies the flattened node array (32 B per node) to host. */
 int rtw_scene_nodes(rtw_ctx* ctx, void* out, uint32_t cap, uint32_t* n_out);
 /* Copies the private BVH of instance `instance` (RTW_INST_BVH, or more than 127 members): 32 B per node, the

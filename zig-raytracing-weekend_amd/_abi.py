@@ -177,6 +177,30 @@ class RtwSceneStats(C.Structure):
                 ("extent", C.c_float), ("box_pad", C.c_float)]
 
 
+RTW_DENOISE_MAX_PASSES = 8
+RTW_DENOISE_DEMODULATE = 1
+
+
+class RtwDenoiseParams(C.Structure):
+    # rtw_denoise_params (32 bytes): the a-trous filter's passes, flags and edge-stopping sigmas (0 = term off)
+    _fields_ = [("passes", C.c_uint32), ("flags", C.c_uint32), ("sigma_color", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("_pad", C.c_float * 3)]
+
+
+def denoise_params(**fields) -> RtwDenoiseParams:
+    """rtw_denoise_defaults() with `fields` overridden; demodulate=True / False sets or clears the flag bit."""
+    p = RtwDenoiseParams()
+    lib().rtw_denoise_defaults(C.byref(p))
+    demod = fields.pop("demodulate", None)
+    for k, v in fields.items():
+        if k.startswith("_") or not hasattr(p, k):
+            raise KeyError(f"rtw_denoise_params has no field {k!r}")
+        setattr(p, k, v)
+    if demod is not None:
+        p.flags = (p.flags | RTW_DENOISE_DEMODULATE) if demod else (p.flags & ~RTW_DENOISE_DEMODULATE)
+    return p
+
+
 # every symbol include/rtw_gpu.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "rtw_version": (C.c_int, []),
@@ -247,6 +271,15 @@ SIGNATURES = {
     "rtw_debug_quad_shade": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "rtw_debug_stripe_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
+    "rtw_denoise_defaults": (None, [C.POINTER(RtwDenoiseParams)]),
+    "rtw_render_guides": (C.c_int, [C.c_void_p, C.POINTER(RtwCamera), C.c_void_p, C.c_void_p]),
+    "rtw_render_guides_device": (C.c_int, [C.c_void_p, C.POINTER(RtwCamera), C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_uint32]),
+    "rtw_denoise": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.POINTER(RtwDenoiseParams), C.c_void_p]),
+    "rtw_denoise_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(RtwDenoiseParams), C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rtw_debug_expneg": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -181,6 +181,18 @@ class RayTraceState:
         """Samples per pixel already in the buffer (writeColor stores the count in .w)."""
         return int(self.writer.buffer[:, 3].max()) if self.writer.buffer.size else 0
 
+    def denoised(self, **params) -> np.ndarray:
+        """The preview of what has been rendered so far: the world's guide buffers for this camera
+        (World.render_guides) and the a-trous filter over the accumulator (World.denoise; params as there).
+        Returns a new accumulator-form buffer -- update_texture-style consumers, the encoders and the
+        checkpoints take it as they take the accumulator -- and leaves the state's own accumulator alone."""
+        cam = self.camera
+        if cam.derived is None:
+            cam.init()
+        guides = self.world.render_guides(cam)
+        return self.world.denoise(self.writer.buffer, guides, cam.derived.image_width, cam.derived.image_height,
+                                  **params)
+
     def checkpoint(self, path: str, spp_done: int) -> None:
         """Write the accumulator + camera/seed/scene hash (rtw_checkpoint_write)."""
         h = C.c_uint64()

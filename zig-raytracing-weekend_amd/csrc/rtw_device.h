@@ -1293,8 +1293,10 @@ RTW_DHD void quad_attr(const rtw_dev_vattr* __restrict__ va, HitPrep& h) {
 template <uint32_t FEAT>
 RTW_DHD HitPrep object_prep(const rtw_launch& L, const Ray& r, uint32_t kind, uint32_t idx,
                                             uint32_t sub, float t) {
-    static_assert((FEAT & RTW_F_ATTR) == 0 || (FEAT & (RTW_F_ALL | RTW_F_TREE)) == (RTW_F_ALL | RTW_F_TREE),
-                  "RTW_F_ATTR only on top of RTW_F_ALL | RTW_F_TREE");
+    // (the guide kernels of rtw_denoise.hip leave RTW_F_MEDIUM out: their rays see through media)
+    static_assert((FEAT & RTW_F_ATTR) == 0 || (FEAT & ((RTW_F_ALL & ~RTW_F_MEDIUM) | RTW_F_TREE)) ==
+                                                  ((RTW_F_ALL & ~RTW_F_MEDIUM) | RTW_F_TREE),
+                  "RTW_F_ATTR only on top of RTW_F_TREE and every scene feature (RTW_F_MEDIUM may be left out)");
     HitPrep h;
     if (kind == RTW_OBJ_QUAD) {
         const rtw_dev_quad q = L.quads[idx];

@@ -693,6 +693,8 @@ void rtw_scene_destroy(rtw_ctx* ctx) {
     if (ctx->d_tl) (void)hipFree(ctx->d_tl);
     if (ctx->d_lights) (void)hipFree(ctx->d_lights);
     if (ctx->d_vattrs) (void)hipFree(ctx->d_vattrs);
+    for (float4* p : ctx->d_dn)
+        if (p) (void)hipFree(p);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -974,6 +976,9 @@ rtw_launch make_launch(const rtw_ctx* ctx, const rtw_camera* c, uint64_t seed) {
 }
 
 }  // namespace
+
+rtw_launch rtw_make_launch(const rtw_ctx* ctx, const rtw_camera* c, uint64_t seed) { return make_launch(ctx, c, seed); }
+int rtw_hip_fail(hipError_t e, const char* where) { return hip_fail(e, where); }
 
 // the camera's part of a launch, and the render-domain key (make_launch; rtw_debug_camera_ray, which has no context)
 void rtw_launch_camera(rtw_launch& L, const rtw_camera* c, uint64_t seed) {
@@ -1289,6 +1294,9 @@ int render_rows_locked(rtw_ctx* ctx, const rtw_camera* cam, uint32_t rpb, uint32
 }
 
 }  // namespace
+
+int rtw_stream_enter(rtw_ctx* ctx, hipStream_t s) { return stream_enter(ctx, s); }
+int rtw_stream_leave(rtw_ctx* ctx, hipStream_t s) { return stream_leave(ctx, s); }
 
 extern "C" {
 

@@ -408,4 +408,15 @@ struct rtw_ctx {
     std::atomic<uint32_t> cpu_calls{0};  // host context: calls rendering now (they share cpu_threads)
     hipEvent_t last_done = nullptr;
     hipStream_t last_stream = nullptr;
+    // the denoiser's two ping-pong images (rtw_denoise.hip), dn_cap pixels each: device float4 planes of a GPU
+    // context, grown on demand under the lock; a host context keeps them in dn_host
+    float4* d_dn[2] = {nullptr, nullptr};
+    uint64_t dn_cap = 0;
+    std::vector<float4> dn_host[2];
 };
+// What the entry points of rtw_denoise.hip share with the render entry points (rtw_host.hip; the caller holds
+// ctx->mu): the launch of a camera on a context, and the stream ordering of consecutive calls on it
+rtw_launch rtw_make_launch(const rtw_ctx* ctx, const rtw_camera* c, uint64_t seed);
+int rtw_stream_enter(rtw_ctx* ctx, hipStream_t s);
+int rtw_stream_leave(rtw_ctx* ctx, hipStream_t s);
+int rtw_hip_fail(hipError_t e, const char* where);  // sets the message, returns RTW_E_OOM / RTW_E_HIP

@@ -374,3 +374,29 @@ RTW_LIBM_FN float rtw_logf(float x_) {
     const float dk = (float)k;
     return s * (hfsq + R) + dk * ln2_lo - hfsq + f + dk * ln2_hi;
 }
+
+// e(x) = exp(-x) for x >= 0, the edge-stopping function of the denoiser (rtw_denoise.hip; the reference calls no
+// exp: this routine is the project's own, checked against float64 exp).  Every operation is one rounded fp32
+// operation, nothing is contracted, so the host and the device agree to the bit:
+//   y = -x;  k = rint(y * log2e)  (to nearest even, |k| <= 126);
+//   r = (y - k * ln2_hi) - k * ln2_lo   (Cody-Waite: ln2_hi has 16 significant bits, so k * ln2_hi is exact);
+//   p = (((((c6 r + c5) r + c4) r + c3) r + c2) r + 1) r + 1,  c_j = 1 / j!  (|r| <= ln2 / 2 + 2^-20);
+//   e = p * 2^k, 2^k made from the exponent bits (k >= -126: normal).
+// 0 above 87 (exp(-87) = 1.6e-38 is the last result above the smallest normal), for +inf and for a NaN; e(0) = 1
+// exactly (k = 0, r = 0, p = 1).  Maximum relative error against float64 exp over [0, 87]: below 2^-21.
+RTW_LIBM_FN float rtw_expneg(float x) {
+    const float log2e = 1.4426950216e+00f, ln2_hi = 6.9314575195e-01f, ln2_lo = 1.4286067653e-06f;
+    const float c2 = 5.0000000000e-01f, c3 = 1.6666667163e-01f, c4 = 4.1666667908e-02f, c5 = 8.3333337679e-03f,
+                c6 = 1.3888889225e-03f;
+    if (!(x <= 87.0f)) return 0.0f;
+    const float y = -x;
+    const float k = __builtin_rintf(y * log2e);
+    const float r = (y - k * ln2_hi) - k * ln2_lo;
+    float p = c6 * r + c5;
+    p = p * r + c4;
+    p = p * r + c3;
+    p = p * r + c2;
+    p = p * r + 1.0f;
+    p = p * r + 1.0f;
+    return p * rtw_lm_float((uint32_t)((int)k + 127) << 23);
+}

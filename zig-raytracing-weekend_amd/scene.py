@@ -729,6 +729,51 @@ class World:
             _abi.check(f(self.handle, q.ctypes.data, a.ctypes.data, n.value, C.byref(n)), "rtw_scene_vertex_attrs_get")
         return q, a
 
+    def render_guides(self, cam) -> tuple:
+        """rtw_render_guides: the first-hit guide buffers of the camera's frame, (albedo, normal_depth), each a
+        float32 (W * H, 4) array in image order.  One deterministic ray per pixel through its centre (no jitter, no
+        defocus, time 0, no seed); media are transparent.  albedo.w = 1 on a hit, 0 on a miss (rgb = the
+        background); normal_depth = (normal towards the ray, depth > 0) on a hit, 0 on a miss.  cam: a Camera (initialised on
+        demand) or an RtwCamera."""
+        c = cam
+        if not isinstance(cam, _abi.RtwCamera):
+            if cam.derived is None:
+                cam.init()
+            c = cam.derived
+        albedo = np.zeros((c.size, 4), np.float32)
+        nd = np.zeros((c.size, 4), np.float32)
+        _abi.check(_abi.lib().rtw_render_guides(self.handle, C.byref(c), albedo.ctypes.data, nd.ctypes.data),
+                   "rtw_render_guides")
+        return albedo, nd
+
+    def denoise(self, accum: np.ndarray, guides, width: int, height: int, out: Optional[np.ndarray] = None,
+                **params) -> np.ndarray:
+        """rtw_denoise: the edge-avoiding a-trous filter over the float4 accumulator `accum` (W * H, 4), guided by
+        guides = (albedo, normal_depth) of render_guides (albedo may be None without demodulation).  params:
+        rtw_denoise_params fields over rtw_denoise_defaults() -- passes, sigma_color, sigma_normal, sigma_depth,
+        flags, or demodulate=True / False.  Returns a new accumulator-form array (rgb = mean * w, w), or fills
+        `out`, which may be `accum` itself."""
+        albedo, nd = guides
+        p = _abi.denoise_params(**params)
+        n = int(width) * int(height)
+
+        def plane(a, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.size != 4 * n:
+                raise ValueError(f"denoise: {name} is not float4[{width} * {height}]")
+            return a
+        acc, albedo, nd = plane(accum, "accum"), plane(albedo, "albedo"), plane(nd, "normal_depth")
+        if out is None:
+            out = np.empty((n, 4), np.float32)
+        if not (isinstance(out, np.ndarray) and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
+                and out.dtype == np.float32 and out.size == 4 * n):
+            raise ValueError(f"denoise: out is not a writable contiguous float32 float4[{width} * {height}]")
+        _abi.check(_abi.lib().rtw_denoise(self.handle, width, height, _abi.ptr(acc), _abi.ptr(albedo), _abi.ptr(nd),
+                                          C.byref(p), out.ctypes.data), "rtw_denoise")
+        return out
+
     def close(self):
         if getattr(self, "handle", None) and self.handle.value:
             _abi.lib().rtw_scene_destroy(self.handle)
