@@ -689,6 +689,76 @@ int rtw_denoise_device(rtw_ctx* ctx, uint32_t width, uint32_t height, const floa
 /* Host-only: out[i] = e(x[i]) = exp(-x[i]), the filter's edge-stopping function (rtw_expneg, the device's code). */
 int rtw_debug_expneg(uint32_t n, const float* x, float* out);
 
+/* ---------------------------------------------------------------------------
+ * Ray queries: the closest hit, or whether anything is hit, for rays the caller supplies -- picking (the object
+ * under the mouse: rtw_trace_rays of one ray of rtw_debug_camera_ray), visibility between points, ambient
+ * occlusion, light-map bakes, an integrator of the caller's own written against first hits.  A caller detects the
+ * capability by the presence of these symbols (the ABI version and every other struct are those of ABI 8).  Kernels
+ * of their own: no render changes by a bit.  DESIGN.md §Ray queries.
+ *
+ * Same walk as a render.  The walk and the hit record of every render's first bounce: the scene's tree with its
+ * hoisted spheres and octant orderings, instance lists and instance trees, the vertex attributes where registered,
+ * tmin = 0.001 and the reference's comparisons (Sphere.hit accepts 0.001 < t, Quad.hit 0.001 <= t).  The same
+ * function runs on the GPU and on a host context: the two agree bit for bit.
+ * Caller's tmax.  A hit is accepted only if t < tmax, whatever the primitive (+inf: unbounded).  A tmax that is not
+ * > 0.001, NaN included, is a miss.
+ * Media.  Rays see through ConstantMedium, as guide rays do: a medium hit needs a path's RNG key, which a bare ray
+ * does not have.
+ * Sphere uv.  Sphere hits always carry Sphere.getSphereUv of the outward normal in uv (a render computes it only
+ * for the textures that read it).
+ * Tied hits.  Of two primitives hit at exactly the same t the one the walk meets first wins (a quad met later at
+ * the same t replaces it, as Quad.hit's closed interval has it in the reference): which one that is depends on the
+ * tree -- the tuning, the BVH mode, whether an instance has a tree.  t itself does not.
+ * Degenerate rays.  A ray with a zero direction, or an infinite or NaN component, gives an unspecified record; the
+ * call still returns (the walks only move forward through their skip links) and no other ray's record is affected.
+ * Far origins.  An origin further out than 7 x the scene's extent (rtw_scene_stats.extent) is walked with the
+ * reference's box arithmetic instead of the FMA slab test, per ray; the hit is the same.
+ * No coherence promise.  One lane walks one ray, in the caller's order: rays that start near each other in the
+ * array and point the same way are faster (profiles/queries/README.md).
+ *
+ * A miss writes t = +inf, kind = index = member = prim_kind = prim_index = RTW_HIT_NONE and every other word 0, so
+ * records can be compared bit for bit.
+ *
+ * rtw_trace_rays / rtw_occluded: host buffers; GPU contexts (staged through a device block of the call's own: the
+ * device form is the fast path) and host contexts (on the context's cpu_threads).
+ * rtw_trace_rays_device / rtw_occluded_device: device buffers of a GPU context (a host context is refused),
+ * enqueued on `stream` (NULL: the context's); flags: RTW_RENDER_NO_SYNC.  The buffers are 16-byte aligned.
+ * rtw_occluded*: out[i] = 1 if any surface is hit on (0.001, tmax), else 0; the walk stops at the first accepted
+ * hit and builds no record.
+ * n = 0 is RTW_OK and touches nothing.  RTW_E_INVALID with a message, outputs untouched: a null context, n above
+ * 2^32 - 1, a null buffer with n > 0, unknown flag bits, a device entry point on a host context.  The calls take the
+ * context lock and order themselves on the stream as renders do.  Out of scope: medium hits, sorting or bucketing
+ * the rays, a 1-bit-per-ray mask, sharding a batch over GPUs (split the array), another tmin.
+ * ------------------------------------------------------------------------- */
+typedef struct rtw_ray {          /* 32 bytes */
+    float origin[3];
+    float tmax;                   /* hits are accepted on the open interval (0.001, tmax); +inf = unbounded */
+    float dir[3];                 /* need not be unit; t is in units of |dir| */
+    float time;                   /* for moving spheres (Sphere.getCenter); 0 otherwise */
+} rtw_ray;
+
+#define RTW_HIT_NONE 0xFFFFFFFFu
+typedef struct rtw_hit {          /* 64 bytes */
+    float t;                      /* p = origin + t dir; +inf on a miss */
+    uint32_t kind;                /* rtw_object_kind of the top-level object: SPHERE, QUAD or INSTANCE; RTW_HIT_NONE on a miss */
+    uint32_t index;               /* into spheres[] / quads[] / instances[] of the scene description */
+    uint32_t member;              /* INSTANCE: position in [0, count) of the member hit; else RTW_HIT_NONE */
+    float p[3];                   /* world-space hit point */
+    uint32_t material;            /* index into materials[] */
+    float normal[3];              /* the record's normal turned towards the ray (world space; the shading normal where
+                                     vertex attributes are registered) */
+    uint32_t front;               /* the geometric front-face test: 1 = the ray meets the outward side */
+    float uv[2];
+    uint32_t prim_kind, prim_index;  /* the primitive itself: the member's sphere / quad for an instance, else
+                                        (kind, index) again */
+} rtw_hit;
+int rtw_trace_rays(rtw_ctx* ctx, uint64_t n, const rtw_ray* rays, rtw_hit* hits);
+int rtw_trace_rays_device(rtw_ctx* ctx, uint64_t n, const rtw_ray* d_rays, rtw_hit* d_hits, void* stream,
+                          uint32_t flags);
+int rtw_occluded(rtw_ctx* ctx, uint64_t n, const rtw_ray* rays, uint8_t* out);
+int rtw_occluded_device(rtw_ctx* ctx, uint64_t n, const rtw_ray* d_rays, uint8_t* d_out, void* stream,
+                        uint32_t flags);
+
 /* Copies the flattened node array (32 B per node) to host. */
 int rtw_scene_nodes(rtw_ctx* ctx, void* out, uint32_t cap, uint32_t* n_out);
 /* Copies the private BVH of instance `instance` (RTW_INST_BVH, or more than 127 members): 32 B per node, the

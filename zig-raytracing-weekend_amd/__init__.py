@@ -9,6 +9,8 @@ Host API (mirrors the reference's Zig API names):
            flatten(objs, lights="emissive" | "emissive+spheres") / World.set_lights: light importance sampling
            Triangle.init(..., normals=, uvs=), Mesh.init(..., normals=, uvs=), load_obj(..., attributes=True) /
            World.set_vertex_attrs: smooth shading and mesh UVs
+           World.trace / World.occluded (numpy), World.trace_device / World.occluded_device (torch; ray_rows,
+           hit_columns): closest-hit and occlusion queries for the caller's own rays
   camera:  Camera (+ init, render(state, task)), SharedStateImageWriter, Task,
            RayTraceState, start_render
   worlds:  generate_world, earth_world, two_spheres_world, two_perlin_world,
@@ -23,4 +25,4 @@ from .camera import (Camera, RayTraceState, SharedStateImageWriter, Task, book1_
 from .scene import (BVHTree, CheckerTexture, ConstantMedium, Dielectric, DiffuseLight,  # noqa: F401
                     HittableList, Image, ImageTexture, Isotropic, Lambertian, Mesh, Metal, NoiseTexture, Perlin, Quad,
                     RotateY, SceneArrays, SolidColor, Sphere, Translate, Triangle, World, createBox, flatten,
-                    load_obj, quad_triangles)
+                    hit_columns, load_obj, quad_triangles, ray_rows)

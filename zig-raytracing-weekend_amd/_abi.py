@@ -201,6 +201,43 @@ def denoise_params(**fields) -> RtwDenoiseParams:
     return p
 
 
+# ray queries (rtw_trace_rays, rtw_occluded): rtw_ray (32 B) and rtw_hit (64 B)
+RTW_HIT_NONE = 0xFFFFFFFF
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmax", "<f4"), ("dir", "<f4", 3), ("time", "<f4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("kind", "<u4"), ("index", "<u4"), ("member", "<u4"),
+                      ("p", "<f4", 3), ("material", "<u4"), ("normal", "<f4", 3), ("front", "<u4"),
+                      ("uv", "<f4", 2), ("prim_kind", "<u4"), ("prim_index", "<u4")])
+assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 64
+# the 4-byte words of the two records, for (N, 8) / (N, 16) tensors: name -> (first word, words, is float)
+RAY_WORDS = {"origin": (0, 3, True), "tmax": (3, 1, True), "dir": (4, 3, True), "time": (7, 1, True)}
+HIT_WORDS = {"t": (0, 1, True), "kind": (1, 1, False), "index": (2, 1, False), "member": (3, 1, False),
+             "p": (4, 3, True), "material": (7, 1, False), "normal": (8, 3, True), "front": (11, 1, False),
+             "uv": (12, 2, True), "prim_kind": (14, 1, False), "prim_index": (15, 1, False)}
+
+
+class RtwRay(C.Structure):
+    _fields_ = [("origin", F3), ("tmax", C.c_float), ("dir", F3), ("time", C.c_float)]
+
+
+class RtwHit(C.Structure):
+    _fields_ = [("t", C.c_float), ("kind", C.c_uint32), ("index", C.c_uint32), ("member", C.c_uint32),
+                ("p", F3), ("material", C.c_uint32), ("normal", F3), ("front", C.c_uint32),
+                ("uv", C.c_float * 2), ("prim_kind", C.c_uint32), ("prim_index", C.c_uint32)]
+
+
+def rays(origins, dirs, tmax=None, time=None) -> np.ndarray:
+    """RAY_DTYPE records of (N, 3) origins and directions (either may be one vector for all); tmax defaults to
+    +inf, time to 0 (scalars or one value per ray)."""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    d = np.asarray(dirs, np.float32).reshape(-1, 3)
+    n = max(len(o), len(d))
+    r = np.zeros(n, RAY_DTYPE)
+    r["origin"], r["dir"] = o, d
+    r["tmax"] = np.inf if tmax is None else np.asarray(tmax, np.float32)
+    r["time"] = 0.0 if time is None else np.asarray(time, np.float32)
+    return r
+
+
 # every symbol include/rtw_gpu.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "rtw_version": (C.c_int, []),
@@ -280,6 +317,10 @@ SIGNATURES = {
     "rtw_denoise_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.POINTER(RtwDenoiseParams), C.c_void_p, C.c_void_p, C.c_uint32]),
     "rtw_debug_expneg": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rtw_trace_rays": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "rtw_trace_rays_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rtw_occluded": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "rtw_occluded_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
 }
 
 _lib = None

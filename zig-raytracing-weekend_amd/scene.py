@@ -774,6 +774,67 @@ class World:
                                           C.byref(p), out.ctypes.data), "rtw_denoise")
         return out
 
+    # ---- ray queries (rtw_trace_rays / rtw_occluded; DESIGN.md §Ray queries)
+    @staticmethod
+    def _rays(origins, dirs, tmax, time) -> np.ndarray:
+        if isinstance(origins, np.ndarray) and origins.dtype == _abi.RAY_DTYPE:
+            if dirs is not None or tmax is not None or time is not None:
+                raise ValueError("ray records carry their own dir, tmax and time")
+            return np.ascontiguousarray(origins).reshape(-1)
+        return _abi.rays(origins, dirs, tmax, time)
+
+    def trace(self, origins, dirs=None, tmax=None, time=None) -> np.ndarray:
+        """rtw_trace_rays: the closest hit of every ray on (0.001, tmax), as HIT_DTYPE records (a miss: t = inf,
+        kind = RTW_HIT_NONE).  origins, dirs: (N, 3); tmax (default inf) and time (default 0): scalars or one per
+        ray -- or `origins` alone as RAY_DTYPE records.  The walk and the hit record of a render's first bounce;
+        media are transparent."""
+        r = self._rays(origins, dirs, tmax, time)
+        hits = np.zeros(len(r), _abi.HIT_DTYPE)
+        _abi.check(_abi.lib().rtw_trace_rays(self.handle, len(r), _abi.ptr(r), _abi.ptr(hits)), "rtw_trace_rays")
+        return hits
+
+    def occluded(self, origins, dirs=None, tmax=None, time=None) -> np.ndarray:
+        """rtw_occluded: a bool per ray, True if any surface is hit on (0.001, tmax).  Arguments as trace()."""
+        r = self._rays(origins, dirs, tmax, time)
+        out = np.zeros(len(r), np.uint8)
+        _abi.check(_abi.lib().rtw_occluded(self.handle, len(r), _abi.ptr(r), _abi.ptr(out)), "rtw_occluded")
+        return out.astype(bool)
+
+    def _query_device(self, name, rays, out, words, dtype, stream):
+        import torch
+        if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2
+                and rays.shape[1] == 8 and rays.is_contiguous()):
+            raise ValueError(f"{name}: rays is not a contiguous (N, 8) float32 CUDA tensor")
+        if rays.device.index != self.device:
+            raise ValueError(f"{name}: rays live on {rays.device}, the world on device {self.device}")
+        n = rays.shape[0]
+        shape = (n, words) if words > 1 else (n,)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=rays.device)
+        if not (isinstance(out, torch.Tensor) and out.device == rays.device and out.dtype == dtype
+                and tuple(out.shape) == shape and out.is_contiguous()):
+            raise ValueError(f"{name}: the output is not a contiguous {shape} {dtype} tensor on {rays.device}")
+        if stream is None:
+            handle, flags = torch.cuda.current_stream(rays.device).cuda_stream, 0
+        else:
+            handle, flags = stream.cuda_stream, _abi.RTW_RENDER_NO_SYNC
+        fn = getattr(_abi.lib(), name)
+        _abi.check(fn(self.handle, n, rays.data_ptr() if n else None, out.data_ptr() if n else None,
+                      C.c_void_p(handle), flags), name)
+        return out
+
+    def trace_device(self, rays, hits=None, stream=None):
+        """rtw_trace_rays_device on torch CUDA tensors: rays (N, 8) float32 -- origin, tmax, dir, time, the words of
+        RAY_DTYPE -- gives hits (N, 16) int32, the words of HIT_DTYPE (hit_columns() names them).  stream=None: on
+        torch's current stream, finished on return; a torch.cuda.Stream: enqueued there, not synchronised."""
+        import torch
+        return self._query_device("rtw_trace_rays_device", rays, hits, 16, torch.int32, stream)
+
+    def occluded_device(self, rays, out=None, stream=None):
+        """rtw_occluded_device on torch CUDA tensors: rays as trace_device(), out (N,) uint8, 1 = occluded."""
+        import torch
+        return self._query_device("rtw_occluded_device", rays, out, 1, torch.uint8, stream)
+
     def close(self):
         if getattr(self, "handle", None) and self.handle.value:
             _abi.lib().rtw_scene_destroy(self.handle)
@@ -807,6 +868,31 @@ class World:
         if n.value:
             _abi.check(f(self.handle, i, out.ctypes.data, n.value, C.byref(n)), "rtw_scene_instance_nodes")
         return out
+
+
+def ray_rows(origins, dirs, tmax=None, time=None):
+    """The (N, 8) float32 tensor World.trace_device() takes, from (N, 3) origin and direction tensors; tmax
+    (default inf) and time (default 0): scalars or (N,) tensors."""
+    import torch
+    n = origins.shape[0]
+    r = torch.empty((n, 8), dtype=torch.float32, device=origins.device)
+    r[:, 0:3], r[:, 4:7] = origins, dirs
+    r[:, 3] = float("inf") if tmax is None else tmax
+    r[:, 7] = 0.0 if time is None else time
+    return r
+
+
+def hit_columns(hits) -> dict:
+    """The named columns of World.trace_device()'s (N, 16) int32 tensor, as views of it: the fields of HIT_DTYPE --
+    t, p, normal, uv as float32, kind, index, member, material, front, prim_kind, prim_index as int32 (RTW_HIT_NONE
+    reads -1) --, and `hit`, a bool tensor, True where the ray hit."""
+    import torch
+    cols = {}
+    for name, (first, words, is_float) in _abi.HIT_WORDS.items():
+        c = hits[:, first:first + words] if words > 1 else hits[:, first]
+        cols[name] = c.view(torch.float32) if is_float else c
+    cols["hit"] = cols["kind"] != -1
+    return cols
 
 
 class BVHTree:
