@@ -40,10 +40,9 @@ __global__ __launch_bounds__(1024) void walk_ceiling(rtw_launch L, uint32_t rays
         const uint32_t x = min((tile % ntx) * 8u + (lane & 7u), L.W - 1u), y = min((tile / ntx) * 8u + (lane >> 3), L.H - 1u);
         rtw_rng rng;
         rng.s = rtw_mix64(L.key0 ^ (((uint64_t)(y * L.W + x) << 32) | k));
-        Ray r = get_ray(L, x + 1u, y + 1u, rng);
+        Ray r = get_ray(L, x + 1u, y + 1u, k, rng);  // ray k of the lane as sample k (its stratum, when strata are on)
         float t;
-        constexpr bool Y4 = CN != 0, F32 = CN == 2;
-        int h = traverse_compact<true, true, Y4, F32>(L, lds, r, t, cnt);
+        int h = traverse_compact<true, true, CN>(L, lds, r, t, cnt);
         walks++;
         if (bounce && h >= 0) {
             const float4* nb = order_base(L.nodes, L, (uint32_t)h >> RTW_HIT_NODE_BITS);
@@ -59,7 +58,7 @@ __global__ __launch_bounds__(1024) void walk_ceiling(rtw_launch L, uint32_t rays
             r2.o = p;
             r2.d = n + divs(u, __builtin_sqrtf(length_squared(u)) + 1e-6f);
             r2.time = 0.0f;
-            h = traverse_compact<true, true, Y4, F32>(L, lds, r2, t, cnt);
+            h = traverse_compact<true, true, CN>(L, lds, r2, t, cnt);
             walks++;
         }
         acc += h >= 0 ? t : 0.0f;

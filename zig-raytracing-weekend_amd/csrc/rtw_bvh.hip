@@ -999,7 +999,7 @@ bool rtw_compact_nodes(const std::vector<rtw_node>& nodes, uint32_t orders, std:
         }
         // per axis the slab the copy's rays enter first (near) and leave last (far):
         // min/max for a non-negative direction component, swapped for a negative one
-        // (orders = 4: x and z by the copy's signs, y as min / max -- traverse_compact<.., Y4> takes the
+        // (orders = 4: x and z by the copy's signs, y as min / max -- traverse_compact<.., CN_F16_4> takes the
         // median of three, which needs no order between the two y slabs)
         uint16_t h[6];
         for (int k = 0; k < 3; k++) {

@@ -16,7 +16,6 @@
 #include <atomic>
 #include <cstdio>
 #include <cstring>
-#include <thread>
 #include <vector>
 
 #include "rtw_device.h"
@@ -56,25 +55,15 @@ void cpu_pixels(const rtw_launch& L, uint32_t a, uint32_t b, float* out, const r
 
 int rtw_cpu_render(const rtw_launch& L, uint32_t begin, uint32_t end, float* out, uint32_t threads,
                    const rtw_render_opts* stop) {
-    const uint32_t n = end - begin;
-    if (threads == 0) threads = std::max(1u, std::thread::hardware_concurrency());
-    threads = std::min<uint32_t>(threads, std::max(1u, n));
     std::atomic<bool> stopped{false};
     // the class once per call: instance trees, registered lights (the mixture-density instantiations) and vertex
     // attributes (always with the trees') select it as they do on the GPU
     decltype(&cpu_pixels<RTW_F_ALL>) pixels = nullptr;
     rtw_with_class<false>(rtw_feat_of(L), [&](auto c) { pixels = cpu_pixels<decltype(c)::value>; });
     // contiguous chunks, as startRender's Tasks (main.zig:318-324); samples in order per pixel
-    auto work = [&](uint32_t t) {
-        const uint32_t a = begin + (uint32_t)((uint64_t)n * t / threads);
-        const uint32_t b = begin + (uint32_t)((uint64_t)n * (t + 1) / threads);
-        pixels(L, a, b, out, stop, stopped);
-    };
-    std::vector<std::thread> pool;
-    pool.reserve(threads);
-    for (uint32_t t = 1; t < threads; t++) pool.emplace_back(work, t);
-    work(0);
-    for (std::thread& th : pool) th.join();
+    rtw_host_ranges(end - begin, threads, 1, [&](uint64_t a, uint64_t b) {
+        pixels(L, begin + (uint32_t)a, begin + (uint32_t)b, out, stop, stopped);
+    });
     return stopped ? RTW_E_CANCELLED : RTW_OK;
 }
 

@@ -27,7 +27,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <thread>
 #include <vector>
 
 #include "rtw_device.h"
@@ -37,26 +36,14 @@ namespace {
 // ---------------------------------------------------------------------------
 // Guides
 // ---------------------------------------------------------------------------
-// the guide classes: every feature but the media (object_leaf gives a medium leaf no hit), with the instance
-// trees, with the vertex attributes.  RTW_F_PDF is irrelevant: nothing scatters.
-constexpr uint32_t kGuideBase = RTW_F_ALL & ~RTW_F_MEDIUM;
-using GuideClasses = RtwClasses<kGuideBase, kGuideBase | RTW_F_TREE, kGuideBase | RTW_F_TREE | RTW_F_ATTR>;
-uint32_t guide_class(const rtw_launch& L) {
-    const uint32_t f = rtw_feat_of(L);
-    if (f & RTW_F_ATTR) return kGuideBase | RTW_F_TREE | RTW_F_ATTR;
-    return (f & RTW_F_TREE) ? (kGuideBase | RTW_F_TREE) : kGuideBase;
-}
-
-// The guides of pixel (x, y): Camera.getRay's pixel centre (camera.zig:171-172) without the jitter, from the
+// (the guide classes: RtwFirstHitClasses, rtw_internal.h)
+// The guides of pixel (x, y): Camera.getRay's pixel centre (pixel_center) without the jitter, from the
 // camera centre, time 0; traverse / hit_prep as every render's first bounce
 template <uint32_t FEAT>
 RTW_DHD void guide_pixel(const rtw_launch& L, uint32_t x, uint32_t y, float4& albedo, float4& nd) {
-    const f3 du = ld3(L.du), dv = ld3(L.dv);
-    const f3 pixel_center =
-        (ld3(L.pixel00) + du * splat((float)(x + L.pixel_offset))) + dv * splat((float)(y + L.pixel_offset));
     Ray r;
     r.o = ld3(L.center);
-    r.d = pixel_center - r.o;
+    r.d = pixel_center(L, x + L.pixel_offset, y + L.pixel_offset) - r.o;
     r.time = 0.0f;
     Counters cnt;
     float t;
@@ -96,19 +83,6 @@ void guides_rows(const rtw_launch& L, uint32_t y0, uint32_t y1, float4* albedo, 
             const size_t p = (size_t)y * L.W + x;
             guide_pixel<FEAT>(L, x, y, albedo[p], nd[p]);
         }
-}
-
-// rows [0, H) in contiguous chunks on `threads` host threads (0: all)
-template <typename F>
-void host_rows(uint32_t H, uint32_t threads, F&& f) {
-    if (threads == 0) threads = std::max(1u, std::thread::hardware_concurrency());
-    threads = std::min(threads, std::max(1u, H));
-    auto work = [&](uint32_t t) { f((uint32_t)((uint64_t)H * t / threads), (uint32_t)((uint64_t)H * (t + 1) / threads)); };
-    std::vector<std::thread> pool;
-    pool.reserve(threads);
-    for (uint32_t t = 1; t < threads; t++) pool.emplace_back(work, t);
-    work(0);
-    for (std::thread& th : pool) th.join();
 }
 
 dim3 pixel_grid(uint32_t W, uint32_t H) { return dim3((W + 31) / 32, (H + 7) / 8); }
@@ -266,28 +240,18 @@ __global__ __launch_bounds__(256) void denoise_pass_lds_kernel(DnPass P) {
 }
 #endif
 
-int invalid(const char* msg) {
-    rtw_set_error(msg);
-    return RTW_E_INVALID;
-}
-#define DN_HIP_TRY(expr)                                          \
-    do {                                                          \
-        hipError_t _e = (expr);                                   \
-        if (_e != hipSuccess) return rtw_hip_fail(_e, #expr);     \
-    } while (0)
-
 bool sigma_ok(float s) { return s >= 0.0f && s <= 3.4028234e38f; }
 
 int check_params(const rtw_ctx* ctx, uint32_t W, uint32_t H, const void* accum, const void* albedo, const void* nd,
                  const rtw_denoise_params* p, const void* out) {
-    if (!ctx || !p || !accum || !nd || !out) return invalid("rtw_denoise: null ctx / params / accum / normal_depth / out");
-    if (p->passes < 1 || p->passes > RTW_DENOISE_MAX_PASSES) return invalid("rtw_denoise: passes outside 1..8");
-    if (p->flags & ~(uint32_t)RTW_DENOISE_DEMODULATE) return invalid("rtw_denoise: unknown flag bits");
+    if (!ctx || !p || !accum || !nd || !out) return rtw_invalid("rtw_denoise: null ctx / params / accum / normal_depth / out");
+    if (p->passes < 1 || p->passes > RTW_DENOISE_MAX_PASSES) return rtw_invalid("rtw_denoise: passes outside 1..8");
+    if (p->flags & ~(uint32_t)RTW_DENOISE_DEMODULATE) return rtw_invalid("rtw_denoise: unknown flag bits");
     if (!sigma_ok(p->sigma_color) || !sigma_ok(p->sigma_normal) || !sigma_ok(p->sigma_depth))
-        return invalid("rtw_denoise: a sigma is negative or not finite");
-    if (W == 0 || H == 0) return invalid("rtw_denoise: width * height == 0");
-    if ((uint64_t)W * H > 0xFFFFFFFFull) return invalid("rtw_denoise: image too large");
-    if ((p->flags & RTW_DENOISE_DEMODULATE) && !albedo) return invalid("rtw_denoise: RTW_DENOISE_DEMODULATE without albedo");
+        return rtw_invalid("rtw_denoise: a sigma is negative or not finite");
+    if (W == 0 || H == 0) return rtw_invalid("rtw_denoise: width * height == 0");
+    if ((uint64_t)W * H > 0xFFFFFFFFull) return rtw_invalid("rtw_denoise: image too large");
+    if ((p->flags & RTW_DENOISE_DEMODULATE) && !albedo) return rtw_invalid("rtw_denoise: RTW_DENOISE_DEMODULATE without albedo");
     return RTW_OK;
 }
 
@@ -316,7 +280,7 @@ int ensure_planes(rtw_ctx* ctx, uint64_t n, hipStream_t s) {
     if (ctx->dn_cap >= n) return RTW_OK;
     uint64_t cap = 0;
     ctx->dn_cap = 0;
-    for (int k = 0; k < 2; k++) DN_HIP_TRY(rtw_device_grow(&ctx->d_dn[k], &cap, n, (size_t)n * 16, s));
+    for (int k = 0; k < 2; k++) HIP_TRY(rtw_device_grow(&ctx->d_dn[k], &cap, n, (size_t)n * 16, s));
     ctx->dn_cap = n;
     return RTW_OK;
 }
@@ -342,7 +306,7 @@ int enqueue_filter(rtw_ctx* ctx, uint32_t W, uint32_t H, const float4* accum, co
 #endif
         hipLaunchKernelGGL(denoise_pass_kernel, g, dim3(256), 0, s, P);
     }
-    DN_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return RTW_OK;
 }
 
@@ -353,12 +317,12 @@ void host_filter(rtw_ctx* ctx, uint32_t W, uint32_t H, const float4* accum, cons
         if (v.size() < n) v.resize(n);
     float4* planes[2] = {ctx->dn_host[0].data(), ctx->dn_host[1].data()};
     const bool demod = (p.flags & RTW_DENOISE_DEMODULATE) != 0;
-    host_rows(H, ctx->cpu_threads, [&](uint32_t y0, uint32_t y1) {
+    rtw_host_ranges(H, ctx->cpu_threads, 1, [&](uint32_t y0, uint32_t y1) {
         for (size_t q = (size_t)y0 * W; q < (size_t)y1 * W; q++) planes[0][q] = dn_prepass(accum[q], demod ? albedo : nullptr, q);
     });
     for (uint32_t i = 0; i < p.passes; i++) {
         const DnPass P = make_pass(W, H, p, i, planes, albedo, nd, out);
-        host_rows(H, ctx->cpu_threads, [&](uint32_t y0, uint32_t y1) {
+        rtw_host_ranges(H, ctx->cpu_threads, 1, [&](uint32_t y0, uint32_t y1) {
             for (uint32_t y = y0; y < y1; y++)
                 for (uint32_t x = 0; x < W; x++)
                     P.dst[(size_t)y * W + x] = dn_filter_pixel(P, DnGlobalTaps{P.src, P.nd, P.W}, x, y);
@@ -385,28 +349,28 @@ void rtw_denoise_defaults(rtw_denoise_params* p) {
 
 int rtw_render_guides_device(rtw_ctx* ctx, const rtw_camera* cam, float* d_albedo, float* d_normal_depth, void* stream,
                              uint32_t flags) {
-    if (!ctx || !d_albedo || !d_normal_depth) return invalid("rtw_render_guides_device: null ctx / albedo / normal_depth");
-    if (ctx->device == RTW_DEVICE_CPU) return invalid("host context: use rtw_render_guides");
+    if (!ctx || !d_albedo || !d_normal_depth) return rtw_invalid("rtw_render_guides_device: null ctx / albedo / normal_depth");
+    if (ctx->device == RTW_DEVICE_CPU) return rtw_invalid("host context: use rtw_render_guides");
     if (int rc = rtw_validate_cam(cam)) return rc;
-    if (flags & ~(uint32_t)RTW_RENDER_NO_SYNC) return invalid("rtw_render_guides_device: unknown flag bits");
+    if (flags & ~(uint32_t)RTW_RENDER_NO_SYNC) return rtw_invalid("rtw_render_guides_device: unknown flag bits");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    DN_HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     if (int rc = rtw_stream_enter(ctx, s)) return rc;
     rtw_launch L = rtw_make_launch(ctx, cam, 0);
     L.counters = nullptr;
-    GuideClasses::visit(guide_class(L), [&](auto c) {
+    RtwFirstHitClasses::visit(rtw_first_hit_class(L), [&](auto c) {
         hipLaunchKernelGGL(guides_kernel<decltype(c)::value>, pixel_grid(L.W, L.H), dim3(256), 0, s, L,
                            reinterpret_cast<float4*>(d_albedo), reinterpret_cast<float4*>(d_normal_depth));
     });
-    DN_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (int rc = rtw_stream_leave(ctx, s)) return rc;
-    if (!(flags & RTW_RENDER_NO_SYNC)) DN_HIP_TRY(hipStreamSynchronize(s));
+    if (!(flags & RTW_RENDER_NO_SYNC)) HIP_TRY(hipStreamSynchronize(s));
     return RTW_OK;
 }
 
 int rtw_render_guides(rtw_ctx* ctx, const rtw_camera* cam, float* albedo, float* normal_depth) {
-    if (!ctx || !albedo || !normal_depth) return invalid("rtw_render_guides: null ctx / albedo / normal_depth");
+    if (!ctx || !albedo || !normal_depth) return rtw_invalid("rtw_render_guides: null ctx / albedo / normal_depth");
     if (int rc = rtw_validate_cam(cam)) return rc;
     if (ctx->device == RTW_DEVICE_CPU) {
         // the lock is held for the whole trace (a frame of single rays is short): the registrations
@@ -416,9 +380,9 @@ int rtw_render_guides(rtw_ctx* ctx, const rtw_camera* cam, float* albedo, float*
         L.counters = nullptr;
         float4* a = reinterpret_cast<float4*>(albedo);
         float4* n = reinterpret_cast<float4*>(normal_depth);
-        GuideClasses::visit(guide_class(L), [&](auto c) {
-            host_rows(L.H, ctx->cpu_threads,
-                      [&](uint32_t y0, uint32_t y1) { guides_rows<decltype(c)::value>(L, y0, y1, a, n); });
+        RtwFirstHitClasses::visit(rtw_first_hit_class(L), [&](auto c) {
+            rtw_host_ranges(L.H, ctx->cpu_threads, 1,
+                            [&](uint32_t y0, uint32_t y1) { guides_rows<decltype(c)::value>(L, y0, y1, a, n); });
         });
         return RTW_OK;
     }
@@ -427,8 +391,8 @@ int rtw_render_guides(rtw_ctx* ctx, const rtw_camera* cam, float* albedo, float*
     float* d = nullptr;
     {
         std::lock_guard<std::mutex> lock(ctx->mu);
-        DN_HIP_TRY(hipSetDevice(ctx->device));
-        DN_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), 2 * nb));
+        HIP_TRY(hipSetDevice(ctx->device));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), 2 * nb));
     }
     int rc = rtw_render_guides_device(ctx, cam, d, d + nb / 4, nullptr, 0);
     hipError_t e = hipSuccess;
@@ -443,10 +407,10 @@ int rtw_denoise_device(rtw_ctx* ctx, uint32_t width, uint32_t height, const floa
                        const float* d_normal_depth, const rtw_denoise_params* params, float* d_out, void* stream,
                        uint32_t flags) {
     if (int rc = check_params(ctx, width, height, d_accum, d_albedo, d_normal_depth, params, d_out)) return rc;
-    if (ctx->device == RTW_DEVICE_CPU) return invalid("host context: use rtw_denoise");
-    if (flags & ~(uint32_t)RTW_RENDER_NO_SYNC) return invalid("rtw_denoise_device: unknown flag bits");
+    if (ctx->device == RTW_DEVICE_CPU) return rtw_invalid("host context: use rtw_denoise");
+    if (flags & ~(uint32_t)RTW_RENDER_NO_SYNC) return rtw_invalid("rtw_denoise_device: unknown flag bits");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    DN_HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     if (int rc = rtw_stream_enter(ctx, s)) return rc;
     if (int rc = enqueue_filter(ctx, width, height, reinterpret_cast<const float4*>(d_accum),
@@ -454,7 +418,7 @@ int rtw_denoise_device(rtw_ctx* ctx, uint32_t width, uint32_t height, const floa
                                 *params, reinterpret_cast<float4*>(d_out), s))
         return rc;
     if (int rc = rtw_stream_leave(ctx, s)) return rc;
-    if (!(flags & RTW_RENDER_NO_SYNC)) DN_HIP_TRY(hipStreamSynchronize(s));
+    if (!(flags & RTW_RENDER_NO_SYNC)) HIP_TRY(hipStreamSynchronize(s));
     return RTW_OK;
 }
 
@@ -472,8 +436,8 @@ int rtw_denoise(rtw_ctx* ctx, uint32_t width, uint32_t height, const float* accu
     float* d = nullptr;
     {
         std::lock_guard<std::mutex> lock(ctx->mu);
-        DN_HIP_TRY(hipSetDevice(ctx->device));
-        DN_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), 3 * nb));
+        HIP_TRY(hipSetDevice(ctx->device));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), 3 * nb));
     }
     hipError_t e = hipMemcpy(d, accum, nb, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d + nf, normal_depth, nb, hipMemcpyHostToDevice);

@@ -126,6 +126,30 @@ RTW_DHD float ubits(uint32_t u) { return __builtin_bit_cast(float, u); }
 
 // ---- RNG helpers (rtweekend.zig / vec3.zig samplers) ----
 RTW_DHD float rnd(rtw_rng& r) { return rtw_path_float(r); }  // render-domain draw
+
+// Rejection sampling of vec3.randomInUnitSphere (D = 3) / randomInUnitDisk (D = 2) (vec3.zig:40-45, 59-64; the
+// disk's z = 0 adds +0 to a non-negative sum: the same value bit for bit): the reference's per-lane loop, each
+// lane drawing from its own counter-based stream: the disk of get_ray and get_ray_wave, the sphere of the split
+// shading forms (random_unit_vector below keeps D = 3 written out).  (The wavefront kernels of sphere scenes share the
+// randomUnitVector loop between the lanes of a wave, wf_reject3: the same draws; the camera's disk loop
+// measured no gain that way)
+template <int D>
+RTW_DHD void seq_reject(rtw_rng& rng, float (&out)[D]) {
+    for (;;) {
+        float w[D];
+        float ls;
+#pragma unroll
+        for (int d = 0; d < D; d++) w[d] = rtw_path_range(rng, -1, 1);
+        if constexpr (D == 3) ls = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+        else ls = w[0] * w[0] + w[1] * w[1];
+        if (ls < 1.0f) {
+#pragma unroll
+            for (int d = 0; d < D; d++) out[d] = w[d];
+            return;
+        }
+    }
+}
+
 RTW_DHD f3 random_unit_vector(rtw_rng& r) {  // vec3.zig:59-68
 #if defined(RTW_ABLATE_REJECT)
     {   // timing ablation only: one candidate, no rejection loop (wrong distribution)
@@ -133,7 +157,7 @@ RTW_DHD f3 random_unit_vector(rtw_rng& r) {  // vec3.zig:59-68
         return unit_vector(mk(x, y, z + 1e-3f));
     }
 #endif
-    for (;;) {
+    for (;;) {  // seq_reject<3>, written out: through it the object-class shade kernels allocate other registers
         float x = rtw_path_range(r, -1, 1);
         float y = rtw_path_range(r, -1, 1);
         float z = rtw_path_range(r, -1, 1);
@@ -220,32 +244,40 @@ RTW_DHD Stratum stratum_of(uint32_t n, uint32_t s) {
 // (built without FMA contraction: a product, then a sum)
 RTW_DHD float stratum_jitter(float cell, float r, float inv) { return ((cell + r) * inv) - 0.5f; }
 
-// Camera.getRay (camera.zig:156-180); c: the sample's stratum (stratum_of), jit (out, may be null): (px, py)
-RTW_DHD Ray get_ray(const rtw_launch& L, uint32_t i, uint32_t j, const Stratum& c, rtw_rng& rng, float* jit = nullptr) {
+// The centre of pixel (i, j) on the pixel plane (camera.zig:171-172): (pixel00 + du i) + dv j
+RTW_DHD f3 pixel_center(const rtw_launch& L, uint32_t i, uint32_t j) {
+    return (ld3(L.pixel00) + ld3(L.du) * splat((float)i)) + ld3(L.dv) * splat((float)j);
+}
+// The jittered point of pixel (i, j) a sample's ray passes through (camera.zig:171-174): two draws, x then y;
+// c: the sample's stratum (stratum_of), jit (out, may be null): (px, py).  get_ray and get_ray_wave start here
+// (the persistent kernel keeps the same lines written out: through this function it takes more registers).
+RTW_DHD f3 pixel_sample(const rtw_launch& L, uint32_t i, uint32_t j, const Stratum& c, rtw_rng& rng,
+                        float* jit = nullptr) {
     const f3 du = ld3(L.du), dv = ld3(L.dv);
-    f3 pixel_center = (ld3(L.pixel00) + du * splat((float)i)) + dv * splat((float)j);
-    float px = stratum_jitter(c.si, rnd(rng), c.inv);
-    float py = stratum_jitter(c.sj, rnd(rng), c.inv);
+    const f3 pc = pixel_center(L, i, j);
+    const float px = stratum_jitter(c.si, rnd(rng), c.inv);
+    const float py = stratum_jitter(c.sj, rnd(rng), c.inv);
     if (jit) {
         jit[0] = px;
         jit[1] = py;
     }
-    f3 pixel_sample = pixel_center + (splat(px) * du + splat(py) * dv);
+    return pc + (splat(px) * du + splat(py) * dv);
+}
+
+// Camera.getRay (camera.zig:156-180); c and jit: pixel_sample's
+RTW_DHD Ray get_ray(const rtw_launch& L, uint32_t i, uint32_t j, const Stratum& c, rtw_rng& rng, float* jit = nullptr) {
+    const f3 ps = pixel_sample(L, i, j, c, rng, jit);
     f3 origin;
     if (L.defocus_angle <= 0) {
         origin = ld3(L.center);
     } else {
-        float dx, dy;
-        for (;;) {  // vec3.randomInUnitDisk (vec3.zig:40-45)
-            dx = rtw_path_range(rng, -1, 1);
-            dy = rtw_path_range(rng, -1, 1);
-            if (dx * dx + dy * dy + 0.0f * 0.0f < 1) break;
-        }
-        origin = (ld3(L.center) + ld3(L.disk_u) * splat(dx)) + ld3(L.disk_v) * splat(dy);
+        float dsk[2];
+        seq_reject<2>(rng, dsk);  // vec3.randomInUnitDisk (vec3.zig:40-45)
+        origin = (ld3(L.center) + ld3(L.disk_u) * splat(dsk[0])) + ld3(L.disk_v) * splat(dsk[1]);
     }
     Ray r;
     r.o = origin;
-    r.d = pixel_sample - origin;
+    r.d = ps - origin;
     r.time = rnd(rng);
     return r;
 }
@@ -419,16 +451,46 @@ struct RayTrav {
     float nk;    // -2^-20 in a VGPR: as an SGPR operand (gfx9 VOP3 has no literal) its FMAs would take 4
                  // clocks instead of dual-issuing at 2 (profiles/r4_valu_peak/)
 };
+// The fast slab test's reciprocal of a direction component: the hardware estimate clamped to |inv| <= 1e30, which
+// keeps every product finite (no inf*0 / inf-inf); a zero component gives slabs of +-1e30 * (P - o), i.e. still
+// +-"infinite" given the >= E*2^-19 box pad
+RTW_DHD float clamped_rcp(float d) { return __builtin_fmaxf(__builtin_fminf(RTW_RCP_EST(d), 1e30f), -1e30f); }
+
+// The two slab tests of a box (A = min corner, B = max corner) on [tmin, tmax]: lo and hi are the entry and exit
+// parameters, and the box is missed when hi <= lo (box_next, inst_box_met) or hi < lo (inst_tree_t, which takes
+// slab_fma from here and keeps the exact form written out).
+//  slab_fma (SAH trees, L.fast_box): t = fma(P, inv, oinv) with inv = clamped_rcp(d) and oinv = -o * inv, min/max
+//    instead of swaps, on boxes padded by E*2^-19 -- conservative (never rejects a box the exact test on the
+//    unpadded box accepts), so the closest hit is unchanged.
+//  slab_exact: Aabb.hit's arithmetic (aabb.zig:82-114), inv = 1 / d.  lo/hi use fmax/fmin: for the NaN slabs of a
+//    zero direction component (0*inf) maxNum keeps the other operand exactly like the reference's
+//    `if (t0 > min) min = t0`, and lo/hi only grow/shrink, so one final comparison equals the per-axis early exit
+//    of aabb.zig:111.
+// (The compact and the two-wide walks store their boxes (near, far) per axis: tests of their own.)
+RTW_DHD void slab_fma(float4 A, float4 B, f3 inv, f3 oinv, float tmin, float tmax, float& lo, float& hi) {
+    const float t0x = __builtin_fmaf(A.x, inv.x, oinv.x), t1x = __builtin_fmaf(B.x, inv.x, oinv.x);
+    const float t0y = __builtin_fmaf(A.y, inv.y, oinv.y), t1y = __builtin_fmaf(B.y, inv.y, oinv.y);
+    const float t0z = __builtin_fmaf(A.z, inv.z, oinv.z), t1z = __builtin_fmaf(B.z, inv.z, oinv.z);
+    lo = __builtin_fmaxf(__builtin_fmaxf(tmin, __builtin_fminf(t0x, t1x)),
+                         __builtin_fmaxf(__builtin_fminf(t0y, t1y), __builtin_fminf(t0z, t1z)));
+    hi = __builtin_fminf(__builtin_fminf(tmax, __builtin_fmaxf(t0x, t1x)),
+                         __builtin_fminf(__builtin_fmaxf(t0y, t1y), __builtin_fmaxf(t0z, t1z)));
+}
+RTW_DHD void slab_exact(float4 A, float4 B, f3 o, f3 inv, float tmin, float tmax, float& lo, float& hi) {
+    float t0x = (A.x - o.x) * inv.x, t1x = (B.x - o.x) * inv.x;
+    float t0y = (A.y - o.y) * inv.y, t1y = (B.y - o.y) * inv.y;
+    float t0z = (A.z - o.z) * inv.z, t1z = (B.z - o.z) * inv.z;
+    if (inv.x < 0) { float tt = t1x; t1x = t0x; t0x = tt; }
+    if (inv.y < 0) { float tt = t1y; t1y = t0y; t0y = tt; }
+    if (inv.z < 0) { float tt = t1z; t1z = t0z; t0z = tt; }
+    lo = __builtin_fmaxf(__builtin_fmaxf(tmin, t0x), __builtin_fmaxf(t0y, t0z));
+    hi = __builtin_fminf(__builtin_fminf(tmax, t1x), __builtin_fminf(t1y, t1z));
+}
+
 RTW_DHD RayTrav ray_trav(const Ray& r, bool fast_box) {
     RayTrav t;
     if (fast_box) {
-        // |inv| <= 1e30 keeps every product finite (no inf*0 / inf-inf); a zero
-        // component gives slabs of +-1e30 * (P - o), i.e. still +-"infinite"
-        // given the >= E*2^-19 box pad
-        auto ci = [](float d) {
-            return __builtin_fmaxf(__builtin_fminf(RTW_RCP_EST(d), 1e30f), -1e30f);
-        };
-        t.inv = mk(ci(r.d.x), ci(r.d.y), ci(r.d.z));
+        t.inv = mk(clamped_rcp(r.d.x), clamped_rcp(r.d.y), clamped_rcp(r.d.z));
         t.oinv = mk(-(r.o.x * t.inv.x), -(r.o.y * t.inv.y), -(r.o.z * t.inv.z));
     } else {
         t.inv = mk(RTW_DIV(1.0f, r.d.x), RTW_DIV(1.0f, r.d.y), RTW_DIV(1.0f, r.d.z));
@@ -490,17 +552,17 @@ RTW_DHD bool sphere_t(f3 center, float radius, const Ray& r, float tmin, float t
     return true;
 }
 
+// Sphere.getCenter (objects.zig:94-98): `base` (center1) of sphere idx at `time`; moving: the sphere's flag, as
+// its record (rtw_dev_sphere.moving) or its leaf (the walk's B.w, an instance tree's low bit of B.w) carries it
 template <uint32_t FEAT>
-RTW_DHD f3 member_sphere_center(const rtw_launch& L, const rtw_dev_sphere& s, uint32_t idx,
-                                                   float time) {
-    f3 c = ld3(s.c1);
+RTW_DHD f3 sphere_center(const rtw_launch& L, f3 base, uint32_t moving, uint32_t idx, float time) {
     if constexpr ((FEAT & RTW_F_MOVING) != 0) {
-        if (s.moving) {  // Sphere.getCenter (objects.zig:94-98)
+        if (moving) {
             const float4 cv = L.cvec[idx];
-            c = c + splat(time) * mk(cv.x, cv.y, cv.z);
+            base = base + splat(time) * mk(cv.x, cv.y, cv.z);
         }
     }
-    return c;
+    return base;
 }
 
 // Quad.hit t only (objects.zig:222-255), closed interval [tmin, tmax]; parallelograms and triangles (rtw_quad.shape)
@@ -587,7 +649,7 @@ RTW_DHD bool list_t(const rtw_launch& L, const rtw_dev_instance* __restrict__ in
         bool h;
         if (RTW_REF_KIND(ref) == RTW_OBJ_SPHERE) {
             const rtw_dev_sphere s = L.sph[idx];
-            h = sphere_t(member_sphere_center<FEAT>(L, s, idx, ro.time), s.radius, ro, tmin, closest, tt);
+            h = sphere_t(sphere_center<FEAT>(L, ld3(s.c1), s.moving, idx, ro.time), s.radius, ro, tmin, closest, tt);
         } else {
             h = quad_t(L.quads[idx], ro, tmin, closest, tt);
         }
@@ -609,8 +671,8 @@ RTW_DHD void load_node(const float4* __restrict__ nodes, uint32_t i, float4& A, 
 //    registers.  The object-space reciprocals are computed once per visit.  Lanes of the wave outside the
 //    instance idle meanwhile, as in list_t's member loop.
 //  * Boxes only cull: they are the members' true object-space boxes padded by the host for origins with
-//    |o| <= reach (the root's b.w), so both slab tests -- the clamped-reciprocal FMA form of box_next with
-//    L.fast_box, else aabb.zig's arithmetic -- keep every box a member test could accept a hit in.  An origin
+//    |o| <= reach (the root's b.w), so both slab tests -- slab_fma on clamped_rcp reciprocals with L.fast_box,
+//    else slab_exact, aabb.zig's arithmetic -- keep every box a member test could accept a hit in.  An origin
 //    beyond reach (a far camera, which also switches the world walk to the exact test) takes list_t.
 //  * Leaves run the list's own tests (sphere_t / quad_t on (tmin, closest), spheres inline in the leaf), so an
 //    accepted t has the list's fp32 value.  Quad.hit accepts t == closest, which in list order lets the later
@@ -630,9 +692,8 @@ RTW_DHD bool inst_tree_t(const rtw_launch& L, const rtw_dev_instance* __restrict
     }
     const bool fast = L.fast_box != 0;
     f3 inv, oinv = mk(0, 0, 0);
-    if (fast) {  // ray_trav's clamped reciprocals
-        auto ci = [](float d) { return __builtin_fmaxf(__builtin_fminf(RTW_RCP_EST(d), 1e30f), -1e30f); };
-        inv = mk(ci(ro.d.x), ci(ro.d.y), ci(ro.d.z));
+    if (fast) {  // as ray_trav
+        inv = mk(clamped_rcp(ro.d.x), clamped_rcp(ro.d.y), clamped_rcp(ro.d.z));
         oinv = mk(-(ro.o.x * inv.x), -(ro.o.y * inv.y), -(ro.o.z * inv.z));
     } else {
         inv = mk(RTW_DIV(1.0f, ro.d.x), RTW_DIV(1.0f, ro.d.y), RTW_DIV(1.0f, ro.d.z));
@@ -653,14 +714,8 @@ RTW_DHD bool inst_tree_t(const rtw_launch& L, const rtw_dev_instance* __restrict
                 h = quad_t(L.quads[idx], ro, tmin, closest, tt);
                 if (h && any_quad && tt == closest && m < sub) h = false;  // the list's later member keeps the tie
             } else {
-                f3 c = mk(A.x, A.y, A.z);
-                if constexpr ((FEAT & RTW_F_MOVING) != 0) {
-                    if (bw & 1u) {  // Sphere.getCenter (objects.zig:94-98), as member_sphere_center
-                        const float4 cv = L.cvec[idx];
-                        c = c + splat(ro.time) * mk(cv.x, cv.y, cv.z);
-                    }
-                }
-                h = sphere_t(c, B.x, ro, tmin, closest, tt);
+                h = sphere_t(sphere_center<FEAT>(L, mk(A.x, A.y, A.z), bw & 1u, idx, ro.time), B.x, ro, tmin, closest,
+                             tt);
             }
             if (h) {
                 closest = tt;
@@ -671,16 +726,10 @@ RTW_DHD bool inst_tree_t(const rtw_launch& L, const rtw_dev_instance* __restrict
             i = w & RTW_SKIP_MASK;
             continue;
         }
-        float lo, hi;
+        float lo, hi;  // box_next's two tests on [tmin, closest]
         if (fast) {
-            const float t0x = __builtin_fmaf(A.x, inv.x, oinv.x), t1x = __builtin_fmaf(B.x, inv.x, oinv.x);
-            const float t0y = __builtin_fmaf(A.y, inv.y, oinv.y), t1y = __builtin_fmaf(B.y, inv.y, oinv.y);
-            const float t0z = __builtin_fmaf(A.z, inv.z, oinv.z), t1z = __builtin_fmaf(B.z, inv.z, oinv.z);
-            lo = __builtin_fmaxf(__builtin_fmaxf(tmin, __builtin_fminf(t0x, t1x)),
-                                 __builtin_fmaxf(__builtin_fminf(t0y, t1y), __builtin_fminf(t0z, t1z)));
-            hi = __builtin_fminf(__builtin_fminf(closest, __builtin_fmaxf(t0x, t1x)),
-                                 __builtin_fminf(__builtin_fmaxf(t0y, t1y), __builtin_fmaxf(t0z, t1z)));
-        } else {  // aabb.zig:82-114 (box_next's exact form) on [tmin, closest]
+            slab_fma(A, B, inv, oinv, tmin, closest, lo, hi);
+        } else {  // slab_exact, written out: through it the ray-query and guide kernels' code moves
             float t0x = (A.x - ro.o.x) * inv.x, t1x = (B.x - ro.o.x) * inv.x;
             float t0y = (A.y - ro.o.y) * inv.y, t1y = (B.y - ro.o.y) * inv.y;
             float t0z = (A.z - ro.o.z) * inv.z, t1z = (B.z - ro.o.z) * inv.z;
@@ -722,7 +771,7 @@ RTW_DHD bool boundary_t(const rtw_launch& L, uint32_t ref, const Ray& r, float t
     switch (RTW_REF_KIND(ref)) {
     case RTW_OBJ_SPHERE: {
         const rtw_dev_sphere s = L.sph[idx];
-        return sphere_t(member_sphere_center<FEAT>(L, s, idx, r.time), s.radius, r, tmin, tmax, t);
+        return sphere_t(sphere_center<FEAT>(L, ld3(s.c1), s.moving, idx, r.time), s.radius, r, tmin, tmax, t);
     }
     case RTW_OBJ_QUAD: return quad_t(L.quads[idx], r, tmin, tmax, t);
     default: {
@@ -770,14 +819,8 @@ RTW_DHD bool medium_t(const rtw_launch& L, uint32_t idx, const Ray& r, float tmi
 RTW_DHD bool inst_box_met(const rtw_launch& L, const rtw_dev_instance* __restrict__ in, const RayTrav& rt,
                                          float closest) {
     if (!(L.fast_box && L.inst_cull)) return true;
-    const float4 A = ldg4(in->box[0]), B = ldg4(in->box[1]);
-    const float t0x = __builtin_fmaf(A.x, rt.inv.x, rt.oinv.x), t1x = __builtin_fmaf(B.x, rt.inv.x, rt.oinv.x);
-    const float t0y = __builtin_fmaf(A.y, rt.inv.y, rt.oinv.y), t1y = __builtin_fmaf(B.y, rt.inv.y, rt.oinv.y);
-    const float t0z = __builtin_fmaf(A.z, rt.inv.z, rt.oinv.z), t1z = __builtin_fmaf(B.z, rt.inv.z, rt.oinv.z);
-    const float lo = __builtin_fmaxf(__builtin_fmaxf(kTmin, __builtin_fminf(t0x, t1x)),
-                                     __builtin_fmaxf(__builtin_fminf(t0y, t1y), __builtin_fminf(t0z, t1z)));
-    const float hi = __builtin_fminf(__builtin_fminf(closest, __builtin_fmaxf(t0x, t1x)),
-                                     __builtin_fminf(__builtin_fmaxf(t0y, t1y), __builtin_fmaxf(t0z, t1z)));
+    float lo, hi;
+    slab_fma(ldg4(in->box[0]), ldg4(in->box[1]), rt.inv, rt.oinv, kTmin, closest, lo, hi);
     return !(hi <= lo);
 }
 
@@ -911,46 +954,22 @@ RTW_DHD void leaf_test(const rtw_launch& L, const Ray& r, const RayTrav& rt, flo
             return;
         }
     }
-    f3 center = mk(A.x, A.y, A.z);
-    if constexpr ((FEAT & RTW_F_MOVING) != 0) {
-        if (fbits(B.w)) {  // Sphere.getCenter (objects.zig:94-98)
-            const float4 cv = L.cvec[fbits(B.z)];
-            center = center + splat(r.time) * mk(cv.x, cv.y, cv.z);
-        }
-    }
-    sphere_leaf(L, r, rt, center, B.x * B.x, i, closest, hit);
+    sphere_leaf(L, r, rt, sphere_center<FEAT>(L, mk(A.x, A.y, A.z), fbits(B.w), fbits(B.z), r.time), B.x * B.x, i,
+                closest, hit);
 }
 
-// Inner node: Aabb.hit (aabb.zig:82-114) with [0.001, closest]; returns the next
-// node (i + 1 = descend, skip = past the subtree).
-//  exact: the reference arithmetic.  hi/lo use fmax/fmin: for the NaN slabs of a
-//    zero direction component (0*inf) maxNum keeps the other operand exactly like
-//    the reference's `if (t0 > min) min = t0`, and lo/hi only grow/shrink, so the
-//    single final `hi <= lo` equals the per-axis early exit of aabb.zig:111.
-//  fast (SAH trees): t = fma(P, inv, -o*inv) with min/max instead of swaps, on
-//    boxes padded by E*2^-19 -- conservative (never rejects a box the exact test
-//    on the unpadded box accepts), so the closest hit is unchanged.
+// Inner node: Aabb.hit (aabb.zig:82-114) with [0.001, closest]; returns the next node (i + 1 = descend, skip =
+// past the subtree).  exact: slab_exact, the reference arithmetic; fast (SAH trees): slab_fma.  (A return in each
+// arm: with one shared `hi <= lo` after them the compiler schedules the walk loop of every caller differently.)
 RTW_DHD uint32_t box_next(const Ray& r, const RayTrav& rt, float4 A, float4 B, uint32_t i,
                                              float closest, bool fast) {
     const uint32_t w = fbits(A.w);
+    float lo, hi;
     if (fast) {
-        const float t0x = __builtin_fmaf(A.x, rt.inv.x, rt.oinv.x), t1x = __builtin_fmaf(B.x, rt.inv.x, rt.oinv.x);
-        const float t0y = __builtin_fmaf(A.y, rt.inv.y, rt.oinv.y), t1y = __builtin_fmaf(B.y, rt.inv.y, rt.oinv.y);
-        const float t0z = __builtin_fmaf(A.z, rt.inv.z, rt.oinv.z), t1z = __builtin_fmaf(B.z, rt.inv.z, rt.oinv.z);
-        const float lo = __builtin_fmaxf(__builtin_fmaxf(kTmin, __builtin_fminf(t0x, t1x)),
-                                         __builtin_fmaxf(__builtin_fminf(t0y, t1y), __builtin_fminf(t0z, t1z)));
-        const float hi = __builtin_fminf(__builtin_fminf(closest, __builtin_fmaxf(t0x, t1x)),
-                                         __builtin_fminf(__builtin_fmaxf(t0y, t1y), __builtin_fmaxf(t0z, t1z)));
+        slab_fma(A, B, rt.inv, rt.oinv, kTmin, closest, lo, hi);
         return (hi <= lo) ? w : i + 1;
     }
-    float t0x = (A.x - r.o.x) * rt.inv.x, t1x = (B.x - r.o.x) * rt.inv.x;
-    float t0y = (A.y - r.o.y) * rt.inv.y, t1y = (B.y - r.o.y) * rt.inv.y;
-    float t0z = (A.z - r.o.z) * rt.inv.z, t1z = (B.z - r.o.z) * rt.inv.z;
-    if (rt.inv.x < 0) { float tt = t1x; t1x = t0x; t0x = tt; }
-    if (rt.inv.y < 0) { float tt = t1y; t1y = t0y; t0y = tt; }
-    if (rt.inv.z < 0) { float tt = t1z; t1z = t0z; t0z = tt; }
-    const float lo = __builtin_fmaxf(__builtin_fmaxf(kTmin, t0x), __builtin_fmaxf(t0y, t0z));
-    const float hi = __builtin_fminf(__builtin_fminf(closest, t1x), __builtin_fminf(t1y, t1z));
+    slab_exact(A, B, r.o, rt.inv, kTmin, closest, lo, hi);
     return (hi <= lo) ? w : i + 1;
 }
 
@@ -980,7 +999,7 @@ RTW_DHD uint32_t trav_step(const float4* __restrict__ nodes, const rtw_launch& L
 // shading finds the leaf.
 // 4 copies (round 5): ordered by the signs of x and z only -- the axes the Book-1 field spreads over
 // (the spheres lie within [0, 2] in y) -- so the compact stage is half the size (rtw_compact_nodes); the
-// walk then takes y's near/far per ray (traverse_compact<.., Y4>).
+// walk then takes y's near/far per ray (traverse_compact<.., CN_F16_4>).
 RTW_DHD uint32_t order_of(const rtw_launch& L, const Ray& r) {
     if (L.n_orders <= 1) return 0;
     if (L.n_orders == 4) return (r.d.x < 0 ? 1u : 0u) | (r.d.z < 0 ? 2u : 0u);
@@ -1049,6 +1068,25 @@ RTW_DHD uint32_t lds_addr(const void* p) {
     return 0;
 #endif
 }
+
+// Counted or not: f(std::bool_constant<counted>).  CNT (every kernel with a counted form): 0 = no device counters
+// (the product launches: their registers and atomics compile away), 1 = the counted pass
+// (rtw_render_opts.counters), 2 = decided per launch by L.counters.  traverse and the compact-LDS walks
+// (walk_clds, rtw_wavefront.hip) choose through it; wf_tile_hit's two callers and traverse_wide2's keep the
+// ternary on L.counters written out: through this function their kernels' code moved
+// (profiles/device_refactor/README.md).
+template <int CNT = 2, typename F>
+RTW_DHD auto with_counted(const rtw_launch& L, F&& f) {
+    if constexpr (CNT != 2) return f(std::bool_constant<CNT == 1>{});
+    else return L.counters ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// The compact node forms a walk can read (traverse_compact's CN):
+//   CN_F16_8  16-B nodes, fp16 boxes, 8 octant copies (the default)
+//   CN_F16_4  16-B nodes, fp16 boxes, 4 copies by the x and z signs (Y4: y slabs by med3)
+//   CN_F32_4  32-B nodes, fp32 boxes for packed FMAs, 4 copies (Y4 and F32; rtw_tuning.compact_nodes 2)
+enum { CN_F16_8 = 0, CN_F16_4 = 1, CN_F32_4 = 2 };
+
 // Y4: the 4-copy layout (L.n_orders == 4; rtw_compact_nodes): x and z stored (near, far) for the copy's
 // signs, y as (min, max) in the near-y / far-y slots.  With ta, tb the two y slab distances, lo = max(X, min(ta,
 // tb)) and hi = min(Y, max(ta, tb)) (X = max(tmin, tnx, tnz), Y = min(closest, tfx, tfz)); the walk uses
@@ -1062,10 +1100,10 @@ RTW_DHD uint32_t lds_addr(const void* p) {
 // pair up on their own: the box step's six FMAs cost 4 + 4 + 2 x 2 clocks instead of six 4-clock
 // v_fma_mix_f32 (profiles/r4_valu_peak/).  The same t = fma(P, inv, -o * inv) on the same fp32 boxes as
 // box_next's fast test: the same visits as the 32-B walk of those boxes, a subset of the fp16 walk's.
-template <bool COUNT, bool LDS = false, bool Y4 = false, bool F32 = false>
+template <bool COUNT, bool LDS = false, int CN = CN_F16_8>
 RTW_DHD int traverse_compact(const rtw_launch& L, const uint4* base, const Ray& r, float& t_out,
                                                 Counters& cnt) {
-    static_assert(!F32 || Y4, "the fp32 nodes are the 4-copy layout");
+    constexpr bool Y4 = CN != CN_F16_8, F32 = CN == CN_F32_4;
     const uint32_t oct = order_of(L, r);
     const char* __restrict__ cb = reinterpret_cast<const char*>(base);
     uint32_t a_base = 0;  // LDS: the stage's LDS address
@@ -1210,14 +1248,14 @@ RTW_DHD int traverse(const float4* __restrict__ nodes, const rtw_launch& L, cons
                                         float& t_out, Counters& cnt, uint64_t mkey = 0) {
     if constexpr (COMPACT && (FEAT & (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_MOVING)) == 0) {
         if (L.cnodes && L.fast_box) {  // per-step counters only in counted passes
-            if (L.cnode32)
-                return L.counters ? traverse_compact<true, false, true, true>(L, L.cnodes, r, t_out, cnt)
-                                  : traverse_compact<false, false, true, true>(L, L.cnodes, r, t_out, cnt);
-            if (L.n_orders == 4)
-                return L.counters ? traverse_compact<true, false, true>(L, L.cnodes, r, t_out, cnt)
-                                  : traverse_compact<false, false, true>(L, L.cnodes, r, t_out, cnt);
-            return L.counters ? traverse_compact<true>(L, L.cnodes, r, t_out, cnt)
-                              : traverse_compact<false>(L, L.cnodes, r, t_out, cnt);
+            auto walk = [&](auto cn) {
+                return with_counted(L, [&](auto c) {
+                    return traverse_compact<decltype(c)::value, false, decltype(cn)::value>(L, L.cnodes, r, t_out, cnt);
+                });
+            };
+            if (L.cnode32) return walk(std::integral_constant<int, CN_F32_4>{});
+            if (L.n_orders == 4) return walk(std::integral_constant<int, CN_F16_4>{});
+            return walk(std::integral_constant<int, CN_F16_8>{});
         }
     }
     const uint32_t oct = order_of(L, r);
@@ -1315,7 +1353,7 @@ RTW_DHD HitPrep object_prep(const rtw_launch& L, const Ray& r, uint32_t kind, ui
         uint32_t mat;
         if (RTW_REF_KIND(ref) == RTW_OBJ_SPHERE) {  // Sphere.hit record (objects.zig:138-147)
             const rtw_dev_sphere s = L.sph[mi];
-            const f3 center = member_sphere_center<FEAT>(L, s, mi, ro.time);
+            const f3 center = sphere_center<FEAT>(L, ld3(s.c1), s.moving, mi, ro.time);
             h.p = ro.o + splat(t) * ro.d;
             const f3 outward = divs(h.p - center, s.radius);
             h.front = dot(ro.d, outward) < 0;
@@ -1348,7 +1386,9 @@ RTW_DHD HitPrep object_prep(const rtw_launch& L, const Ray& r, uint32_t kind, ui
     return h;
 }
 
-// The material kind of a walk's hit (the record hit_prep reads, without the hit record itself)
+// The material kind of a walk's hit (the record hit_prep reads, without the hit record itself).  The hit id is
+// taken apart here, in hit_prep and in the ray queries' record (rtw_query.hip) in the same words: every shared
+// decoder tried moved the code of the sphere kernels (profiles/device_refactor/README.md).
 template <uint32_t FEAT>
 RTW_DHD uint32_t hit_material_kind(const float4* __restrict__ nodes, const rtw_launch& L, int hit) {
     if (L.n_orders > 1) {
@@ -1390,13 +1430,7 @@ RTW_DHD HitPrep hit_prep(const float4* __restrict__ nodes, const rtw_launch& L, 
     }
     const float4 A = nodes[2 * hit];
     const float4 B = nodes[2 * hit + 1];
-    f3 center = mk(A.x, A.y, A.z);
-    if constexpr ((FEAT & RTW_F_MOVING) != 0) {
-        if (fbits(B.w)) {
-            const float4 cv = L.cvec[fbits(B.z)];
-            center = center + splat(r.time) * mk(cv.x, cv.y, cv.z);
-        }
-    }
+    const f3 center = sphere_center<FEAT>(L, mk(A.x, A.y, A.z), fbits(B.w), fbits(B.z), r.time);
     HitPrep h;
     h.p = r.o + splat(t) * r.d;
     h.uv.outward = divs(h.p - center, B.x);
@@ -1599,42 +1633,12 @@ RTW_DHD bool shade(const float4* __restrict__ nodes, const rtw_launch& L, const 
     return scatter_finish<FEAT>(L, r, h, ruv, rng, thr, acc, att, sc);
 }
 
-// ---------------------------------------------------------------------------
-// Rejection sampling of vec3.randomInUnitSphere (D = 3) / randomInUnitDisk
-// (D = 2) (vec3.zig:40-45, 59-64): the reference's per-lane loop, each lane
-// drawing from its own counter-based stream.  (The wavefront kernels of sphere
-// scenes share the randomUnitVector loop between the lanes of a wave, wf_reject3:
-// the same draws; the camera's disk loop measured no gain that way)
-// ---------------------------------------------------------------------------
-template <int D>
-RTW_DHD void seq_reject(rtw_rng& rng, float (&out)[D]) {
-    for (;;) {
-        float w[D];
-        float ls;
-#pragma unroll
-        for (int d = 0; d < D; d++) w[d] = rtw_path_range(rng, -1, 1);
-        if constexpr (D == 3) ls = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-        else ls = w[0] * w[0] + w[1] * w[1];
-        if (ls < 1.0f) {
-#pragma unroll
-            for (int d = 0; d < D; d++) out[d] = w[d];
-            return;
-        }
-    }
-}
-
 // Camera.getRay for every lane of the wave (`active` lanes get a ray): the same
 // draws in the same order as get_ray, the disk's rejection loop outside the
 // per-lane branch (one loop for the wave); c: the sample's stratum, the same for the whole wave.
 RTW_DHD Ray get_ray_wave(const rtw_launch& L, bool active, uint32_t i, uint32_t j, const Stratum& c, rtw_rng& rng) {
-    const f3 du = ld3(L.du), dv = ld3(L.dv);
-    f3 pixel_sample = mk(0, 0, 0);
-    if (active) {
-        const f3 pixel_center = (ld3(L.pixel00) + du * splat((float)i)) + dv * splat((float)j);
-        const float px = stratum_jitter(c.si, rnd(rng), c.inv);
-        const float py = stratum_jitter(c.sj, rnd(rng), c.inv);
-        pixel_sample = pixel_center + (splat(px) * du + splat(py) * dv);
-    }
+    f3 ps = mk(0, 0, 0);
+    if (active) ps = pixel_sample(L, i, j, c, rng);
     f3 origin = ld3(L.center);
     if (L.defocus_angle > 0) {
         float dsk[2] = {0.0f, 0.0f};
@@ -1643,7 +1647,7 @@ RTW_DHD Ray get_ray_wave(const rtw_launch& L, bool active, uint32_t i, uint32_t 
     }
     Ray r;
     r.o = origin;
-    r.d = pixel_sample - origin;
+    r.d = ps - origin;
     r.time = active ? rnd(rng) : 0.0f;
     return r;
 }

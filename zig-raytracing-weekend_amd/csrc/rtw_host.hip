@@ -27,18 +27,12 @@ int fail(int code, const char* msg) {
     return code;
 }
 
-int hip_fail(hipError_t e, const char* where) {
+}  // namespace
+
+int rtw_hip_fail(hipError_t e, const char* where) {
     g_err = std::string(where) + ": " + hipGetErrorString(e);
     return e == hipErrorOutOfMemory ? RTW_E_OOM : RTW_E_HIP;
 }
-
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t _e = (expr);                         \
-        if (_e != hipSuccess) return hip_fail(_e, #expr); \
-    } while (0)
-
-}  // namespace
 
 void rtw_set_error(const char* msg) { g_err = msg ? msg : ""; }
 
@@ -337,7 +331,7 @@ int upload_blob(rtw_ctx* ctx, const std::vector<uint8_t>& blob) {
     if (e == hipSuccess) e = hipMemcpy(ctx->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc(&ctx->d_dbg, 64 * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&ctx->d_work, 256);
-    return e == hipSuccess ? RTW_OK : hip_fail(e, "rtw_scene_create upload");
+    return e == hipSuccess ? RTW_OK : rtw_hip_fail(e, "rtw_scene_create upload");
 }
 
 // the launch's scene pointers: the sections of the blob at `base` (the device copy, or a host context's own)
@@ -978,7 +972,6 @@ rtw_launch make_launch(const rtw_ctx* ctx, const rtw_camera* c, uint64_t seed) {
 }  // namespace
 
 rtw_launch rtw_make_launch(const rtw_ctx* ctx, const rtw_camera* c, uint64_t seed) { return make_launch(ctx, c, seed); }
-int rtw_hip_fail(hipError_t e, const char* where) { return hip_fail(e, where); }
 
 // the camera's part of a launch, and the render-domain key (make_launch; rtw_debug_camera_ray, which has no context)
 void rtw_launch_camera(rtw_launch& L, const rtw_camera* c, uint64_t seed) {
@@ -1071,7 +1064,7 @@ int run_wavefront(rtw_ctx* ctx, rtw_launch L, hipStream_t stream, rtw_timer* T) 
             const size_t bytes = wf_state_bytes(slots(need), need);
             const hipError_t e = rtw_device_grow(&ctx->d_wf, &ctx->wf_cap, need, bytes, stream);
             if (e == hipSuccess) break;
-            if (e != hipErrorOutOfMemory || n_s == 1) return hip_fail(e, "wavefront path state");
+            if (e != hipErrorOutOfMemory || n_s == 1) return rtw_hip_fail(e, "wavefront path state");
             (void)hipGetLastError();  // clear the sticky OOM before the retry
             n_s = (n_s + 1) / 2;
             need = n_pix * n_s;
@@ -1130,7 +1123,7 @@ int run_wavefront(rtw_ctx* ctx, rtw_launch L, hipStream_t stream, rtw_timer* T) 
         ctx->wf_stripe_cap = W.stripe_cap;
         rtw_wavefront_batch(L, W, stream, ctx->n_cu, T);
         hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "wavefront launch");
+        if (e != hipSuccess) return rtw_hip_fail(e, "wavefront launch");
     }
     return RTW_OK;
 }
@@ -1154,7 +1147,7 @@ int run_batches(rtw_ctx* ctx, rtw_launch L, uint32_t s0, uint32_t s1, uint32_t b
             rtw_launch_render(L, stream, ctx->variant, ctx->grid);
             RTW_TIME_END(T)
             hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return hip_fail(e, "render launch");
+            if (e != hipSuccess) return rtw_hip_fail(e, "render launch");
         }
         if (polled) {
             HIP_TRY(hipStreamSynchronize(stream));
@@ -1400,7 +1393,7 @@ int rtw_render_ex(rtw_ctx* ctx, const rtw_camera* cam, uint32_t pix_begin, uint3
         ctx->host_calls--;
     }
     ctx->host_cv.notify_all();
-    if (e != hipSuccess) return hip_fail(e, "rtw_render copy back");
+    if (e != hipSuccess) return rtw_hip_fail(e, "rtw_render copy back");
     return rc;
 }
 
@@ -1489,7 +1482,7 @@ int rtw_render_rows(rtw_ctx* ctx, const rtw_camera* cam, uint32_t rpb, uint32_t 
                                 &ctl, rows);
     hipError_t e = hipMemcpyAsync(tile, ctx->d_rows, nb, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(e, "rtw_render_rows copy back");
+    if (e != hipSuccess) return rtw_hip_fail(e, "rtw_render_rows copy back");
     ctx->last_stream = nullptr;  // synchronised
     return rc;
 }

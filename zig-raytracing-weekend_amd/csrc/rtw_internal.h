@@ -7,7 +7,9 @@
 
 #include <condition_variable>
 #include <atomic>
+#include <algorithm>
 #include <mutex>
+#include <thread>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -171,6 +173,17 @@ using RtwObjectClasses =
     RtwClasses<RTW_F_ALL, RTW_F_ALL | RTW_F_TREE, RTW_F_ALL | RTW_F_PDF, RTW_F_ALL | RTW_F_TREE | RTW_F_PDF,
                RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR, RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>;
 using RtwSphereClasses = RtwClasses<0u, RTW_F_CHECKER>;
+// The classes of the first-hit kernels -- the guide buffers (rtw_denoise.hip) and the ray queries (rtw_query.hip),
+// where nothing scatters (RTW_F_PDF is irrelevant): every feature but the media (object_leaf gives a medium leaf
+// no hit: a medium hit needs a path's RNG key), with the instance trees, with the vertex attributes.
+constexpr uint32_t kRtwFirstHitBase = RTW_F_ALL & ~RTW_F_MEDIUM;
+using RtwFirstHitClasses =
+    RtwClasses<kRtwFirstHitBase, kRtwFirstHitBase | RTW_F_TREE, kRtwFirstHitBase | RTW_F_TREE | RTW_F_ATTR>;
+inline uint32_t rtw_first_hit_class(const rtw_launch& L) {
+    const uint32_t f = rtw_feat_of(L);
+    if (f & RTW_F_ATTR) return kRtwFirstHitBase | RTW_F_TREE | RTW_F_ATTR;
+    return (f & RTW_F_TREE) ? (kRtwFirstHitBase | RTW_F_TREE) : kRtwFirstHitBase;
+}
 // Calls f with the class of the features `feat` (rtw_feat_of): one of the six object classes, or with SPHERES
 // (the persistent kernel) also one of the two sphere-scene classes, which the other kernels run as RTW_F_ALL.
 template <bool SPHERES, typename F>
@@ -419,4 +432,31 @@ struct rtw_ctx {
 rtw_launch rtw_make_launch(const rtw_ctx* ctx, const rtw_camera* c, uint64_t seed);
 int rtw_stream_enter(rtw_ctx* ctx, hipStream_t s);
 int rtw_stream_leave(rtw_ctx* ctx, hipStream_t s);
-int rtw_hip_fail(hipError_t e, const char* where);  // sets the message, returns RTW_E_OOM / RTW_E_HIP
+
+// The error helpers of every host file: a failed HIP call sets the thread's message and returns RTW_E_OOM /
+// RTW_E_HIP (rtw_host.hip), a refused argument sets it and returns RTW_E_INVALID.
+int rtw_hip_fail(hipError_t e, const char* where);
+inline int rtw_invalid(const char* msg) {
+    rtw_set_error(msg);
+    return RTW_E_INVALID;
+}
+#define HIP_TRY(expr)                                         \
+    do {                                                      \
+        hipError_t _e = (expr);                               \
+        if (_e != hipSuccess) return rtw_hip_fail(_e, #expr); \
+    } while (0)
+
+// The host backend's thread pool: [0, n) in contiguous chunks [n t / T, n (t + 1) / T) -- startRender's Tasks
+// (main.zig:318-324) -- on T host threads, T = threads (0: all the machine's) but at most max(1, n / min_chunk); the
+// calling thread takes chunk 0.  f(begin, end) runs once per chunk.  (n < 2^32: n * T stays in 64 bits.)
+template <typename F>
+void rtw_host_ranges(uint64_t n, uint32_t threads, uint64_t min_chunk, F&& f) {
+    if (threads == 0) threads = std::max(1u, std::thread::hardware_concurrency());
+    threads = (uint32_t)std::min<uint64_t>(threads, std::max<uint64_t>(1, n / min_chunk));
+    auto work = [&](uint32_t t) { f(n * t / threads, n * (t + 1) / threads); };
+    std::vector<std::thread> pool;
+    pool.reserve(threads);
+    for (uint32_t t = 1; t < threads; t++) pool.emplace_back(work, t);
+    work(0);
+    for (std::thread& th : pool) th.join();
+}

@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256, WAVES) void render_persistent_v1(rtw_launch L)
         {
             const bool starting = st == ST_NEWSAMPLE;
             f3 pixel_sample = mk(0, 0, 0);
-            if (starting) {
+            if (starting) {  // (pixel_sample of rtw_device.h, written out: see there)
                 rng.s = rtw_mix64(L.key0 ^ (((uint64_t)pixel << 32) | (uint64_t)s));
                 const f3 du = ld3(L.du), dv = ld3(L.dv);
                 const f3 pixel_center = (ld3(L.pixel00) + du * splat((float)px)) + dv * splat((float)py);
@@ -316,34 +316,9 @@ __global__ void debug_rng_kernel(uint64_t seed, uint32_t pixel, uint32_t sample,
     for (uint32_t k = 0; k < n; k++) out[k] = rtw_path_float(r);
 }
 
-// Diagnostic: for every bounce of one sample, brute-force all leaves with the
-// exact test and with the fast-reject filter; record the first leaf the filter
-// would wrongly reject (out[8..]).
-__device__ void debug_filter_check(const rtw_launch& L, const Ray& r, float* out) {
-    const RayTrav rt = ray_trav(r, L.fast_box != 0);
-    for (uint32_t i = 0; i < L.n_nodes; i++) {
-        const float4 A = L.nodes[2 * i];
-        const float4 B = L.nodes[2 * i + 1];
-        if (!(fbits(A.w) & RTW_LEAF_BIT)) continue;
-        const f3 oc = r.o - mk(A.x, A.y, A.z);
-        const float half_b = dot(oc, r.d);
-        const float c = length_squared(oc) - B.x * B.x;
-        const float disc = half_b * half_b - rt.a * c;
-        if (!(disc >= 0)) continue;
-        const float sq = __builtin_sqrtf(disc);
-        const float r1 = (-half_b - sq) / rt.a, r2 = (-half_b + sq) / rt.a;
-        const bool acc_exact = (kTmin < r1) || (kTmin < r2);
-        const float sa = __builtin_amdgcn_sqrtf(disc);
-        const float e = (__builtin_fabsf(half_b) + sa) * rt.rcp_a * 3.8146973e-06f;
-        const float q1 = (-half_b - sa) * rt.rcp_a, q2 = (-half_b + sa) * rt.rcp_a;
-        const bool acc_fast = (q1 + e > kTmin) || (q2 + e > kTmin);
-        if (acc_exact && !acc_fast && out[8] == 0) {
-            out[8] = 1; out[9] = (float)i; out[10] = half_b; out[11] = c; out[12] = disc; out[13] = sq; out[14] = sa;
-            out[15] = rt.a; out[16] = rt.rcp_a; out[17] = r1; out[18] = r2; out[19] = q1; out[20] = q2; out[21] = e;
-        }
-    }
-}
-
+// Diagnostic (rtw_debug_sample): one sample's radiance and counters (out[0..5]), then the path replayed with every
+// bounce's walk checked against a brute-force exact closest hit over all leaves (the first mismatch: out[22..30]).
+// (The sphere filter itself, sphere_may_hit, is checked against the exact roots on the host: tests/test_filter.py.)
 template <uint32_t FEAT>
 __global__ void debug_sample_kernel(rtw_launch L, uint32_t pixel, uint32_t sample, float* out) {
     if (threadIdx.x | blockIdx.x) return;
@@ -357,14 +332,12 @@ __global__ void debug_sample_kernel(rtw_launch L, uint32_t pixel, uint32_t sampl
     out[3] = (float)cnt.rays;
     out[4] = (float)cnt.nodes;
     out[5] = (float)cnt.leaves;
-    // replay the path to run the filter check on every bounce ray
     rtw_rng rng;
     rng.s = rtw_mix64(L.key0 ^ (((uint64_t)pixel << 32) | (uint64_t)sample));
     Ray r = get_ray(L, x + L.pixel_offset, y + L.pixel_offset, sample, rng);
     f3 acc = mk(0, 0, 0), thr = mk(1, 1, 1);
     int bounce = 0;
     for (uint32_t depth = L.max_depth; depth > 0; depth--, bounce++) {
-        debug_filter_check(L, r, out);
         float t;
         const int hit = traverse<FEAT>(L.nodes, L, r, t, cnt, rng.s);
         // brute-force exact closest over all leaves

@@ -24,23 +24,13 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <thread>
 #include <vector>
 
 #include "rtw_device.h"
 
 namespace {
 
-// the guide classes (rtw_denoise.hip): every feature but the media (object_leaf gives a medium leaf no hit: a
-// medium hit needs a path's RNG key), with the instance trees, with the vertex attributes
-constexpr uint32_t kQueryBase = RTW_F_ALL & ~RTW_F_MEDIUM;
-using QueryClasses = RtwClasses<kQueryBase, kQueryBase | RTW_F_TREE, kQueryBase | RTW_F_TREE | RTW_F_ATTR>;
-uint32_t query_class(const rtw_launch& L) {
-    const uint32_t f = rtw_feat_of(L);
-    if (f & RTW_F_ATTR) return kQueryBase | RTW_F_TREE | RTW_F_ATTR;
-    return (f & RTW_F_TREE) ? (kQueryBase | RTW_F_TREE) : kQueryBase;
-}
-
+// (the query classes: RtwFirstHitClasses, rtw_internal.h)
 // rtw_ray as two float4: (origin, tmax), (dir, time)
 RTW_DHD Ray query_ray(float4 a, float4 b) {
     Ray r;
@@ -170,29 +160,6 @@ __global__ __launch_bounds__(256) void query_any_kernel(rtw_launch L, float reac
     out[i] = query_any<FEAT>(L, Lx, reach, rays[2 * i], rays[2 * i + 1]);
 }
 
-// rays [0, n) in contiguous chunks on `threads` host threads (0: all)
-template <typename F>
-void host_ranges(uint64_t n, uint32_t threads, F&& f) {
-    if (threads == 0) threads = std::max(1u, std::thread::hardware_concurrency());
-    threads = (uint32_t)std::min<uint64_t>(threads, std::max<uint64_t>(1, n / 64));
-    auto work = [&](uint32_t t) { f(n * t / threads, n * (t + 1) / threads); };
-    std::vector<std::thread> pool;
-    pool.reserve(threads);
-    for (uint32_t t = 1; t < threads; t++) pool.emplace_back(work, t);
-    work(0);
-    for (std::thread& th : pool) th.join();
-}
-
-int invalid(const char* msg) {
-    rtw_set_error(msg);
-    return RTW_E_INVALID;
-}
-#define Q_HIP_TRY(expr)                                           \
-    do {                                                          \
-        hipError_t _e = (expr);                                   \
-        if (_e != hipSuccess) return rtw_hip_fail(_e, #expr);     \
-    } while (0)
-
 // the scene's launch without a camera, and the reach of the FMA slab test
 rtw_launch query_launch(const rtw_ctx* ctx, float& reach) {
     rtw_launch L = ctx->base;
@@ -206,16 +173,16 @@ int check_args(const char* what, const rtw_ctx* ctx, uint64_t n, const void* ray
     char msg[128];
     if (!ctx) {
         std::snprintf(msg, sizeof msg, "%s: null ctx", what);
-        return invalid(msg);
+        return rtw_invalid(msg);
     }
     if (n > 0xFFFFFFFFull) {
         std::snprintf(msg, sizeof msg, "%s: more than 2^32 - 1 rays", what);
-        return invalid(msg);
+        return rtw_invalid(msg);
     }
     if (n == 0) return 1;
     if (!rays || !out) {
         std::snprintf(msg, sizeof msg, "%s: null rays / output", what);
-        return invalid(msg);
+        return rtw_invalid(msg);
     }
     return RTW_OK;
 }
@@ -224,20 +191,20 @@ int check_args(const char* what, const rtw_ctx* ctx, uint64_t n, const void* ray
 template <bool ANY>
 int query_device(const char* what, rtw_ctx* ctx, uint64_t n, const rtw_ray* d_rays, void* d_out, void* stream,
                  uint32_t flags) {
-    if (ctx && ctx->device == RTW_DEVICE_CPU) return invalid("host context: use the host-buffer entry point");
-    if (flags & ~(uint32_t)RTW_RENDER_NO_SYNC) return invalid("ray query: unknown flag bits");
+    if (ctx && ctx->device == RTW_DEVICE_CPU) return rtw_invalid("host context: use the host-buffer entry point");
+    if (flags & ~(uint32_t)RTW_RENDER_NO_SYNC) return rtw_invalid("ray query: unknown flag bits");
     if (const int rc = check_args(what, ctx, n, d_rays, d_out)) return rc == 1 ? RTW_OK : rc;
     // the kernels read rays and write hits as float4 (the occlusion flags are bytes)
-    if (((uintptr_t)d_rays | (ANY ? 0 : (uintptr_t)d_out)) & 15) return invalid("ray query: device rays / hits not 16-byte aligned");
+    if (((uintptr_t)d_rays | (ANY ? 0 : (uintptr_t)d_out)) & 15) return rtw_invalid("ray query: device rays / hits not 16-byte aligned");
     std::lock_guard<std::mutex> lock(ctx->mu);
-    Q_HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     if (int rc = rtw_stream_enter(ctx, s)) return rc;
     float reach;
     const rtw_launch L = query_launch(ctx, reach);
     const dim3 grid((uint32_t)((n + 255) / 256));
     const float4* rays = reinterpret_cast<const float4*>(d_rays);
-    QueryClasses::visit(query_class(L), [&](auto c) {
+    RtwFirstHitClasses::visit(rtw_first_hit_class(L), [&](auto c) {
         if constexpr (ANY)
             hipLaunchKernelGGL(query_any_kernel<decltype(c)::value>, grid, dim3(256), 0, s, L, reach, n, rays,
                                static_cast<uint8_t*>(d_out));
@@ -245,9 +212,9 @@ int query_device(const char* what, rtw_ctx* ctx, uint64_t n, const rtw_ray* d_ra
             hipLaunchKernelGGL(query_closest_kernel<decltype(c)::value>, grid, dim3(256), 0, s, L, reach, n, rays,
                                static_cast<float4*>(d_out));
     });
-    Q_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (int rc = rtw_stream_leave(ctx, s)) return rc;
-    if (!(flags & RTW_RENDER_NO_SYNC)) Q_HIP_TRY(hipStreamSynchronize(s));
+    if (!(flags & RTW_RENDER_NO_SYNC)) HIP_TRY(hipStreamSynchronize(s));
     return RTW_OK;
 }
 
@@ -262,9 +229,9 @@ int query_host(const char* what, rtw_ctx* ctx, uint64_t n, const rtw_ray* rays, 
         float reach;
         const rtw_launch L = query_launch(ctx, reach);
         const rtw_launch Lx = exact_box(L);
-        QueryClasses::visit(query_class(L), [&](auto c) {
+        RtwFirstHitClasses::visit(rtw_first_hit_class(L), [&](auto c) {
             constexpr uint32_t FEAT = decltype(c)::value;
-            host_ranges(n, ctx->cpu_threads, [&](uint64_t i0, uint64_t i1) {
+            rtw_host_ranges(n, ctx->cpu_threads, 64, [&](uint64_t i0, uint64_t i1) {  // chunks of at least 64 rays
                 for (uint64_t i = i0; i < i1; i++) {
                     float4 r[2];
                     std::memcpy(r, rays + i, sizeof r);
@@ -284,8 +251,8 @@ int query_host(const char* what, rtw_ctx* ctx, uint64_t n, const rtw_ray* rays, 
     char* d = nullptr;
     {
         std::lock_guard<std::mutex> lock(ctx->mu);
-        Q_HIP_TRY(hipSetDevice(ctx->device));
-        Q_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), in_bytes + out_bytes));
+        HIP_TRY(hipSetDevice(ctx->device));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), in_bytes + out_bytes));
     }
     hipError_t e = hipMemcpy(d, rays, in_bytes, hipMemcpyHostToDevice);
     int rc = RTW_OK;

@@ -634,16 +634,13 @@ __device__ __forceinline__ rtw_launch stage_geom(const rtw_launch& L, float4* ld
     return G;
 }
 
-// The compact node forms a walk can read (traverse_compact):
-//   CN_F16_8  16-B nodes, fp16 boxes, 8 octant copies (the default)
-//   CN_F16_4  16-B nodes, fp16 boxes, 4 copies by the x and z signs (y slabs by med3)
-//   CN_F32_4  32-B nodes, fp32 boxes for packed FMAs, 4 copies (rtw_tuning.compact_nodes 2)
-enum { CN_F16_8 = 0, CN_F16_4 = 1, CN_F32_4 = 2 };
-// uint4s per node of the launch's compact form
+// uint4s per node of the launch's compact form (CN_*, rtw_device.h)
 __device__ __forceinline__ uint32_t cn_quads(const rtw_launch& L) { return L.cnode32 ? 2u : 1u; }
-template <bool COUNT, bool LDS, int CN>
-__device__ __forceinline__ int walk_compact(const rtw_launch& L, const uint4* base, const Ray& r, float& t, Counters& cnt) {
-    return traverse_compact<COUNT, LDS, CN != CN_F16_8, CN == CN_F32_4>(L, base, r, t, cnt);
+// the walk over the compact nodes staged in LDS (stage_clds), counted as CNT says (with_counted)
+template <int CN, int CNT = 2>
+__device__ __forceinline__ int walk_clds(const rtw_launch& L, const uint4* lds, const Ray& r, float& t, Counters& cnt) {
+    return with_counted<CNT>(
+        L, [&](auto c) { return traverse_compact<decltype(c)::value, true, CN>(L, lds, r, t, cnt); });
 }
 
 // every copy of the compact nodes into this block's LDS, inner nodes' skip offsets rebased to
@@ -1105,8 +1102,7 @@ __global__ __launch_bounds__(1024) void wf_trace_clds(rtw_launch L, rtw_wf W, ui
             const Ray r = wf_input_ray<FEAT, CAM>(L, W, S, slot, it, depth, rng, txy, true);
             if (depth) {
                 float t;
-                const int h = L.counters ? walk_compact<true, true, CN>(L, wf_clds, r, t, cnt)
-                                         : walk_compact<false, true, CN>(L, wf_clds, r, t, cnt);
+                const int h = walk_clds<CN>(L, wf_clds, r, t, cnt);
                 W.hit[slot] = make_float2(t, __int_as_float(h));
                 cnt.rays++;
             }
@@ -1305,11 +1301,8 @@ __device__ __forceinline__ void wf_tail_body(const rtw_launch& L, const rtw_wf& 
             }
             float t;
             int hit;
-            if constexpr (CLDS && CNT == 2)
-                hit = L.counters ? walk_compact<true, true, CN>(L, lds, r, t, cnt)
-                                 : walk_compact<false, true, CN>(L, lds, r, t, cnt);
-            else if constexpr (CLDS)
-                hit = walk_compact<CNT == 1, true, CN>(L, lds, r, t, cnt);
+            if constexpr (CLDS)
+                hit = walk_clds<CN, CNT>(L, lds, r, t, cnt);
             else
                 hit = nodes ? traverse<FEAT, false>(nodes, L, r, t, cnt, rng.s)  // the LDS stage
                             : wf_traverse_global<FEAT>(L, r, t, cnt, rng.s);
@@ -1478,8 +1471,8 @@ void wf_tail_clds2(rtw_launch L, rtw_wf W, uint32_t it) {
 //   WALK_CLDS   the compact nodes of every octant copy staged in LDS (small static sphere SAH trees, C2)
 //   WALK_LDS    the 32-B node array of one ordering staged in LDS (small object scenes: Cornell)
 //   WALK_GLOBAL L.cnodes / L.nodes through L1/L2 (large trees: C4)
-//   WALK_CLDS4  the compact nodes of the 4 (x, z)-sign copies staged in LDS (traverse_compact<.., Y4>)
-//   WALK_CLDS32 the 32-B fp32-box nodes of the 4 copies staged in LDS (traverse_compact<.., Y4, F32>)
+//   WALK_CLDS4  the compact nodes of the 4 (x, z)-sign copies staged in LDS (traverse_compact<.., CN_F16_4>)
+//   WALK_CLDS32 the 32-B fp32-box nodes of the 4 copies staged in LDS (traverse_compact<.., CN_F32_4>)
 enum { WALK_CLDS = 0, WALK_LDS = 1, WALK_GLOBAL = 2, WALK_CLDS4 = 3, WALK_CLDS32 = 4 };
 template <int WALK>
 constexpr int walk_cn() { return WALK == WALK_CLDS32 ? CN_F32_4 : WALK == WALK_CLDS4 ? CN_F16_4 : CN_F16_8; }
@@ -1488,10 +1481,7 @@ template <uint32_t FEAT, int WALK, int CNT = 2>
 __device__ __forceinline__ int wf_walk(const rtw_launch& L, const void* lds, const Ray& r, float& t, Counters& cnt,
                                        uint64_t mkey) {
     if constexpr (WALK == WALK_CLDS || WALK == WALK_CLDS4 || WALK == WALK_CLDS32) {
-        const uint4* cn = static_cast<const uint4*>(lds);
-        if constexpr (CNT != 2) return walk_compact<CNT == 1, true, walk_cn<WALK>()>(L, cn, r, t, cnt);
-        return L.counters ? walk_compact<true, true, walk_cn<WALK>()>(L, cn, r, t, cnt)
-                          : walk_compact<false, true, walk_cn<WALK>()>(L, cn, r, t, cnt);
+        return walk_clds<walk_cn<WALK>(), CNT>(L, static_cast<const uint4*>(lds), r, t, cnt);
     } else if constexpr (WALK == WALK_LDS) {
         return traverse<FEAT, false>(static_cast<const float4*>(lds), L, r, t, cnt, mkey);  // the LDS stage
     } else {
