@@ -622,6 +622,64 @@ int rtw_scene_set_vertex_attrs(rtw_ctx* ctx, const uint32_t* quads, const rtw_ve
 int rtw_scene_vertex_attrs_get(rtw_ctx* ctx, uint32_t* quads, rtw_vertex_attr* attrs, uint32_t cap, uint32_t* n_out);
 
 /* ---------------------------------------------------------------------------
+ * Environment maps: image-based lighting with importance sampling.  A caller detects the
+ * capability by the presence of these symbols (the ABI version and every struct are those of
+ * ABI 8).  With an environment registered, a ray that leaves the scene adds thr * env(d) instead
+ * of the camera's background -- at every bounce, camera rays included, whatever background_mode
+ * says -- and rtw_render_guides* report env(d) as a miss's albedo.rgb.  Ray queries are untouched.
+ *   env(d): d' = (c d.x - s d.z, d.y, s d.x + c d.z) with s, c the sine and cosine of rotate_y as
+ *     RotateY.init takes them (radians = degrees * pi / 180 in fp32, then sin / cos);
+ *     (u, v) = sphere_uv(unit_vector(d')); column floor(clamp(u) W), row floor((1 - clamp(v)) H),
+ *     both clamped to the map (texture_value's image lookup, nearest texel, row 0 = +y); the
+ *     texel's radiance, scale * texel, one fp32 product per channel taken at registration.
+ *   RTW_ENV_SAMPLE: the map is light number n_lights of the mixture density of
+ *     rtw_scene_set_lights: the uniform pick is over n_lights + 1, the draw order stays s, then (if
+ *     s < 0.5) k, a, b, and the light density is the sum over the lights plus
+ *     D(texel of d) / max(sin(theta_d), 2^-12), divided by n_lights + 1.  The texel weights are
+ *     lum(scale * texel) * sin(pi (row + 0.5) / H), lum = 0.2126 r + 0.7152 g + 0.0722 b; the
+ *     marginal (rows) and conditional (columns) distributions are built in fp64 and stored as
+ *     fp32, their last entries exactly 1; b picks the row and a the column -- the smallest index
+ *     whose entry exceeds the draw --, each draw remapped linearly inside its cell; the direction
+ *     is sphere_uv's inverse.  A map whose weights sum to 0 renders with sampling off.  Lambertian
+ *     and Isotropic scatter use the mixture; Metal, Dielectric and emission are unchanged.
+ * Plain fp32 in one association on every backend (DESIGN.md §Environment maps), so a GPU context
+ * and a host context render the same bits.  Scenes of spheres alone take an environment too: they
+ * then render with the general kernels instead of their own (slower; profiles/environment/).
+ * Out of scope: bilinear filtering; maps above RTW_ENV_MAX_WIDTH x RTW_ENV_MAX_HEIGHT; an
+ * environment hidden from camera rays; rotation about other axes; environment hits in ray
+ * queries; a filter for the direct view of an HDR sun (its pixels alias as the map's texels do).
+ * ------------------------------------------------------------------------- */
+#define RTW_ENV_MAX_WIDTH 4096
+#define RTW_ENV_MAX_HEIGHT 2048
+enum { RTW_ENV_SAMPLE = 1u };         /* the map is also a light of the mixture density */
+typedef struct rtw_environment {
+    const float* rgb;                 /* width*height*3 floats, row-major, row 0 = +y (top): linear radiance, no 8-bit clamp */
+    uint32_t width, height;
+    float scale[3];                   /* radiance = scale * texel */
+    float rotate_y;                   /* degrees about y, sin/cos taken as RotateY.init takes them */
+    uint32_t flags;                   /* RTW_ENV_* */
+    uint32_t _pad;
+} rtw_environment;
+/* Registers the environment (env == NULL clears: the context then renders exactly as one that
+ * never had one, bit for bit).  The map is copied at the call: the caller's memory is read once.
+ * Refused with RTW_E_INVALID, the offender named in rtw_last_error and the registered
+ * environment left as it was: a null rgb, a zero dimension or one above the maxima, a texel or
+ * scale that is negative, NaN or infinite, a non-finite rotate_y, unknown flag bits.  Must not
+ * race a render on ctx.  Works on GPU and host contexts.  rtw_scene_hash covers the map, scale,
+ * rotation and flags; rtw_multi_create refuses contexts whose environments differ. */
+int rtw_scene_set_environment(rtw_ctx* ctx, const rtw_environment* env);
+/* Copies the registered environment as given: *out (rgb = NULL; width = height = 0 when none is
+ * registered) and, if rgb is non-NULL, at most cap_floats floats of the map. */
+int rtw_scene_environment_get(rtw_ctx* ctx, rtw_environment* out, float* rgb, uint64_t cap_floats);
+/* Host-only test hook: the device's environment functions -- the same fp32 operations -- on a
+ * context of either kind.  For dirs[3i..] the radiance env(d), the density
+ * D / max(sin(theta), 2^-12) of the map's own sampler (0 when the map is not sampled) and the
+ * texel looked up (row * width + column); for draws[2i..] = (a, b) the sampled direction.  Any
+ * pointer may be NULL.  RTW_E_INVALID without a registered environment. */
+int rtw_debug_environment(rtw_ctx* ctx, uint32_t n, const float* dirs, const float* draws,
+                          float* radiance, float* pdf, float* sampled_dir, uint32_t* texel);
+
+/* ---------------------------------------------------------------------------
  * Denoised previews: first-hit guide buffers and an edge-avoiding a-trous filter (Dammertz et al. 2010) over the
  * accumulator, for the handful of samples per pixel an interactive viewer shows.  A caller detects the capability
  * by the presence of these symbols (the ABI version and every struct are those of ABI 8).  Kernels of their own:

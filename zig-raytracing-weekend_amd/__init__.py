@@ -9,6 +9,8 @@ Host API (mirrors the reference's Zig API names):
            flatten(objs, lights="emissive" | "emissive+spheres") / World.set_lights: light importance sampling
            Triangle.init(..., normals=, uvs=), Mesh.init(..., normals=, uvs=), load_obj(..., attributes=True) /
            World.set_vertex_attrs: smooth shading and mesh UVs
+           Environment(rgb, scale, rotate_y, sample) / Environment.load_hdr, flatten(objs, environment=) /
+           World.set_environment: image-based lighting, importance-sampled (worlds.sky_sun: a procedural sky)
            World.trace / World.occluded (numpy), World.trace_device / World.occluded_device (torch; ray_rows,
            hit_columns): closest-hit and occlusion queries for the caller's own rays
   camera:  Camera (+ init, render(state, task)), SharedStateImageWriter, Task,
@@ -22,7 +24,7 @@ from ._abi import RtwError, lib  # noqa: F401
 from .camera import (Camera, RayTraceState, SharedStateImageWriter, Task, book1_camera,  # noqa: F401
                      cornell_camera, cornell_smoke_camera, earth_perlin_camera, next_week_camera, progressive_render,
                      simple_light_camera, start_render)
-from .scene import (BVHTree, CheckerTexture, ConstantMedium, Dielectric, DiffuseLight,  # noqa: F401
+from .scene import (BVHTree, CheckerTexture, ConstantMedium, Dielectric, DiffuseLight, Environment,  # noqa: F401
                     HittableList, Image, ImageTexture, Isotropic, Lambertian, Mesh, Metal, NoiseTexture, Perlin, Quad,
                     RotateY, SceneArrays, SolidColor, Sphere, Translate, Triangle, World, createBox, flatten,
                     hit_columns, load_obj, quad_triangles, ray_rows)

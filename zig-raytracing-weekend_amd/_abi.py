@@ -36,6 +36,8 @@ RTW_DEAL_SMALL_SORT, RTW_DEAL_ALL = 128, 187
 RTW_DEVICE_CPU = -1
 RTW_MAX_LIGHTS = 16
 RTW_MAX_STRATA = 256  # rtw_camera.strata: n x n jitter cells per pixel, n^2 <= 2^16
+RTW_ENV_MAX_WIDTH, RTW_ENV_MAX_HEIGHT = 4096, 2048  # rtw_environment: the largest map
+RTW_ENV_SAMPLE = 1  # rtw_environment.flags: the map is also a light of the mixture density
 
 # numpy record layouts == the C structs (asserted against sizeof in tests)
 SPHERE_DT = np.dtype([("center1", "<f4", 3), ("radius", "<f4"), ("center2", "<f4", 3), ("is_moving", "<u4"),
@@ -201,6 +203,12 @@ def denoise_params(**fields) -> RtwDenoiseParams:
     return p
 
 
+class RtwEnvironment(C.Structure):
+    # rtw_environment (40 bytes): an equirectangular radiance map, row 0 = +y
+    _fields_ = [("rgb", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("scale", F3),
+                ("rotate_y", C.c_float), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 # ray queries (rtw_trace_rays, rtw_occluded): rtw_ray (32 B) and rtw_hit (64 B)
 RTW_HIT_NONE = 0xFFFFFFFF
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmax", "<f4"), ("dir", "<f4", 3), ("time", "<f4")])
@@ -296,6 +304,10 @@ SIGNATURES = {
     "rtw_scene_lights_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rtw_scene_set_vertex_attrs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "rtw_scene_vertex_attrs_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "rtw_scene_set_environment": (C.c_int, [C.c_void_p, C.POINTER(RtwEnvironment)]),
+    "rtw_scene_environment_get": (C.c_int, [C.c_void_p, C.POINTER(RtwEnvironment), C.c_void_p, C.c_uint64]),
+    "rtw_debug_environment": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "rtw_scene_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rtw_scene_instance_nodes": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rtw_debug_rng": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),

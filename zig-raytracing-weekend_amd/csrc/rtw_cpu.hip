@@ -221,6 +221,46 @@ extern "C" int rtw_debug_quad_shade(uint32_t n, const rtw_quad* quads, const rtw
     return RTW_OK;
 }
 
+// Host-only test hook (include/rtw_gpu.h), and a symbol a caller detects environment maps by: env_texel,
+// env_radiance, env_pdf and env_sample -- the device's code, the same fp32 operations -- on the context's host copy
+// of the registered block (a GPU context keeps one too)
+extern "C" int rtw_debug_environment(rtw_ctx* ctx, uint32_t n, const float* dirs, const float* draws, float* radiance,
+                                     float* pdf, float* sampled_dir, uint32_t* texel) {
+    if (!ctx) {
+        rtw_set_error("null ctx");
+        return RTW_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (ctx->env_block.empty()) {
+        rtw_set_error("rtw_debug_environment: no environment is registered");
+        return RTW_E_INVALID;
+    }
+    const rtw_dev_env& e = *reinterpret_cast<const rtw_dev_env*>(ctx->env_block.data());
+    for (uint32_t i = 0; i < n; i++) {
+        if (dirs) {
+            const f3 d = ld3(dirs + 3 * (size_t)i);
+            float st;
+            const uint32_t t = env_texel(e, d, st);
+            if (texel) texel[i] = t;
+            if (radiance) {
+                const f3 c = env_radiance(e, d);
+                radiance[3 * (size_t)i] = c.x;
+                radiance[3 * (size_t)i + 1] = c.y;
+                radiance[3 * (size_t)i + 2] = c.z;
+            }
+            if (pdf) pdf[i] = e.sampled ? env_pdf(e, d) : 0.0f;
+        }
+        if (draws && sampled_dir) {
+            f3 s = mk(0, 0, 0);
+            if (e.sampled) s = env_sample(e, draws[2 * (size_t)i], draws[2 * (size_t)i + 1]);
+            sampled_dir[3 * (size_t)i] = s.x;
+            sampled_dir[3 * (size_t)i + 1] = s.y;
+            sampled_dir[3 * (size_t)i + 2] = s.z;
+        }
+    }
+    return RTW_OK;
+}
+
 // Host-only test hook (include/rtw_gpu.h): the slot arithmetic of the bucketed push's LDS cursors
 // (rtw_wavefront.h wf_cursor_*, the device's code) for n pushing lanes
 extern "C" int rtw_debug_push_cursor(uint32_t n, const uint32_t* blk, const uint32_t* old, const uint32_t* fresh,

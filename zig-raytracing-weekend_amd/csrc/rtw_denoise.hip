@@ -36,7 +36,7 @@ namespace {
 // ---------------------------------------------------------------------------
 // Guides
 // ---------------------------------------------------------------------------
-// (the guide classes: RtwFirstHitClasses, rtw_internal.h)
+// (the guide classes: RtwFirstHitClasses and, with an environment registered, RtwGuideEnvClasses, rtw_internal.h)
 // The guides of pixel (x, y): Camera.getRay's pixel centre (pixel_center) without the jitter, from the
 // camera centre, time 0; traverse / hit_prep as every render's first bounce
 template <uint32_t FEAT>
@@ -49,7 +49,7 @@ RTW_DHD void guide_pixel(const rtw_launch& L, uint32_t x, uint32_t y, float4& al
     float t;
     const int hit = traverse<FEAT>(L.nodes, L, r, t, cnt, 0);
     if (hit < 0) {
-        const f3 bg = background(L, r);
+        const f3 bg = background<FEAT>(L, r);
         albedo = make_float4(bg.x, bg.y, bg.z, 0.0f);
         nd = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
@@ -359,10 +359,11 @@ int rtw_render_guides_device(rtw_ctx* ctx, const rtw_camera* cam, float* d_albed
     if (int rc = rtw_stream_enter(ctx, s)) return rc;
     rtw_launch L = rtw_make_launch(ctx, cam, 0);
     L.counters = nullptr;
-    RtwFirstHitClasses::visit(rtw_first_hit_class(L), [&](auto c) {
+    auto launch = [&](auto c) {
         hipLaunchKernelGGL(guides_kernel<decltype(c)::value>, pixel_grid(L.W, L.H), dim3(256), 0, s, L,
                            reinterpret_cast<float4*>(d_albedo), reinterpret_cast<float4*>(d_normal_depth));
-    });
+    };
+    if (!RtwFirstHitClasses::visit(rtw_guide_class(L), launch)) (void)RtwGuideEnvClasses::visit(rtw_guide_class(L), launch);
     HIP_TRY(hipGetLastError());
     if (int rc = rtw_stream_leave(ctx, s)) return rc;
     if (!(flags & RTW_RENDER_NO_SYNC)) HIP_TRY(hipStreamSynchronize(s));
@@ -380,10 +381,11 @@ int rtw_render_guides(rtw_ctx* ctx, const rtw_camera* cam, float* albedo, float*
         L.counters = nullptr;
         float4* a = reinterpret_cast<float4*>(albedo);
         float4* n = reinterpret_cast<float4*>(normal_depth);
-        RtwFirstHitClasses::visit(rtw_first_hit_class(L), [&](auto c) {
+        auto rows = [&](auto c) {
             rtw_host_ranges(L.H, ctx->cpu_threads, 1,
                             [&](uint32_t y0, uint32_t y1) { guides_rows<decltype(c)::value>(L, y0, y1, a, n); });
-        });
+        };
+        if (!RtwFirstHitClasses::visit(rtw_guide_class(L), rows)) (void)RtwGuideEnvClasses::visit(rtw_guide_class(L), rows);
         return RTW_OK;
     }
     // GPU context: the two guides through a device staging block of this call's

@@ -1270,7 +1270,90 @@ RTW_DHD int traverse(const float4* __restrict__ nodes, const rtw_launch& L, cons
     return hit_with_order(hit, oct);
 }
 
+// ---------------------------------------------------------------------------
+// Environment maps (RTW_F_ENV kernels; rtw_scene_set_environment, DESIGN.md §Environment maps).  Every operation
+// below is plain fp32 in one association, the same on the host and the device (no estimates, no contraction).
+// ---------------------------------------------------------------------------
+// The floor of sin(theta) in the map's density: it bites within 2^-12 rad of the poles, two caps of
+// 2 pi (1 - cos(2^-12)) = 1.87e-7 sr each (the bound on the bias).
+constexpr float kEnvSinFloor = 0x1p-12f;
+constexpr float kEnvBelowOne = 0x1.fffffep-1f;  // the largest fp32 below 1
+
+// world direction -> the map's frame (RotateY.hit's ray transform, objects.zig:401-411) and back
+RTW_DHD f3 env_to_map(const rtw_dev_env& e, f3 d) {
+    return mk(e.cos_y * d.x - e.sin_y * d.z, d.y, e.sin_y * d.x + e.cos_y * d.z);
+}
+RTW_DHD f3 env_to_world(const rtw_dev_env& e, f3 d) {
+    return mk(e.cos_y * d.x + e.sin_y * d.z, d.y, -e.sin_y * d.x + e.cos_y * d.z);
+}
+// The texel of world direction d, row * width + column: unit_vector, sphere_uv, then the clamps and floors of
+// texture_value's image branch (row floor((1 - v) H): row 0 = +y).  sin_theta (out): sin of the polar angle,
+// sqrt(x x + z z) of the unit vector -- no cancellation near the poles --, floored.
+RTW_DHD uint32_t env_texel(const rtw_dev_env& e, f3 d, float& sin_theta) {
+    const f3 ud = unit_vector(env_to_map(e, d));
+    float u, v;
+    sphere_uv(ud, u, v);
+    const float nu = u < 0 ? 0 : (u > 1 ? 1 : u);
+    const float nv = 1.0f - (v < 0 ? 0 : (v > 1 ? 1 : v));
+    const uint32_t i = (uint32_t)__builtin_floorf(nu * (float)e.width);
+    const uint32_t j = (uint32_t)__builtin_floorf(nv * (float)e.height);
+    const uint32_t x = i < e.width ? i : e.width - 1;   // (a NaN direction: (uint32_t)NaN, clamped like any other)
+    const uint32_t y = j < e.height ? j : e.height - 1;
+    const float st = __builtin_sqrtf(ud.x * ud.x + ud.z * ud.z);
+    sin_theta = st > kEnvSinFloor ? st : kEnvSinFloor;
+    return y * e.width + x;
+}
+// env(d): one 16-B load
+RTW_DHD f3 env_radiance(const rtw_dev_env& e, f3 d) {
+    float st;
+    const float4 t = e.texels[env_texel(e, d, st)];
+    return mk(t.x, t.y, t.z);
+}
+// the density of the map's sampler at world direction d: D(texel of d) / max(sin(theta_d), 2^-12)
+RTW_DHD float env_pdf(const rtw_dev_env& e, f3 d) {
+    float st;
+    const float4 t = e.texels[env_texel(e, d, st)];
+    return RTW_DIV(t.w, st);
+}
+// The smallest index k of the n-entry cumulative table c with c[k] > x (c[n - 1] = 1 > x: it exists), and x
+// remapped linearly inside the cell (c[k - 1], c[k]] to [0, 1).  An entry equal to its predecessor -- a row or a
+// texel of no weight -- is never the smallest.  ceil(log2 n) loads, each lane its own chain.
+RTW_DHD uint32_t env_search(const float* __restrict__ c, uint32_t n, float x, float& frac) {
+    uint32_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (c[mid] > x) hi = mid;
+        else lo = mid + 1;
+    }
+    const float c0 = lo ? c[lo - 1] : 0.0f, c1 = c[lo];
+    const float f = RTW_DIV(x - c0, c1 - c0);
+    frac = f < kEnvBelowOne ? (f > 0.0f ? f : 0.0f) : kEnvBelowOne;  // (x >= 1 or a NaN draw: the cell's far end)
+    return lo;
+}
+// A direction of the map's density from the draws (a, b): b picks the row and a the column, the direction is
+// sphere_uv's inverse at (u, v) = ((i + fa) / W, 1 - (j + fb) / H), turned back to the world.
+RTW_DHD f3 env_sample(const rtw_dev_env& e, float a, float b) {
+    float fa, fb;
+    const uint32_t j = env_search(e.marginal, e.height, b, fb);
+    const uint32_t i = env_search(e.conditional + (size_t)j * e.width, e.width, a, fa);
+    const float u = RTW_DIV((float)i + fa, (float)e.width);
+    const float v = 1.0f - RTW_DIV((float)j + fb, (float)e.height);
+    const float theta = v * kPi, phi = u * (2 * kPi);
+    const float sn = rtw_sinf(theta);
+    return env_to_world(e, mk(-(sn * rtw_cosf(phi)), -rtw_cosf(theta), sn * rtw_sinf(phi)));
+}
+// is the map a light of the mixture density? (RTW_F_ENV kernels; the other classes have no map)
+template <uint32_t FEAT>
+RTW_DHD uint32_t env_lights(const rtw_launch& L) {
+    if constexpr ((FEAT & RTW_F_ENV) != 0) return rtw_env_of(L)->sampled ? 1u : 0u;
+    return 0u;
+}
+
+// The radiance of a ray that leaves the scene: the registered environment's (RTW_F_ENV kernels: one is
+// registered), else the camera's background.
+template <uint32_t FEAT>
 RTW_DHD f3 background(const rtw_launch& L, const Ray& r) {
+    if constexpr ((FEAT & RTW_F_ENV) != 0) return env_radiance(*rtw_env_of(L), r.d);
     if (L.bg_mode == RTW_BG_GRADIENT) {  // camera.zig:204-206
         f3 ud = unit_vector(r.d);
         float a = 0.5f * (ud.y + 1.0f);
@@ -1470,6 +1553,7 @@ RTW_DHD float sphere_omc(float r, float dist2) {
 // light k at t >= 0.001 (Quad.hit / Sphere.hit on its own: occlusion plays no part in a density), else 0.
 // Quad: pk = t^2 |d|^2 / (|dot(d, n_k)| / |d| * area_k) (a triangle: its own interior test and area).  Sphere: pk = 1 / (2 pi (1 - cos(theta_max))), the
 // uniform density over the cone the sphere subtends.  n and every record's kind are wave-uniform.
+template <uint32_t FEAT>
 RTW_DHD float light_pdf(const rtw_launch& L, f3 o, f3 d) {
     Ray lr;
     lr.o = o;
@@ -1494,6 +1578,11 @@ RTW_DHD float light_pdf(const rtw_launch& L, f3 o, f3 d) {
             sum = sum + RTW_DIV((t * t) * dd, cosine * lt.area);
         }
     }
+    // the environment, light number n when it is sampled: no hit test -- every direction meets it
+    if constexpr ((FEAT & RTW_F_ENV) != 0) {
+        const rtw_dev_env* e = rtw_env_of(L);
+        if (e->sampled) return RTW_DIV(sum + env_pdf(*e, d), (float)(n + 1u));
+    }
     return RTW_DIV(sum, (float)n);
 }
 
@@ -1502,18 +1591,24 @@ RTW_DHD float light_pdf(const rtw_launch& L, f3 o, f3 d) {
 // the wave-shared rejection loops and needs_unit_vector are those of the kernels without lights): s; then,
 // only if s < 0.5, the light k, then a, then b (two draws for either kind of light).  False: the sample lies below the horizon (pdf_scatter == 0),
 // the path ends.  Otherwise w = pdf_scatter / (0.5 pdf_light + 0.5 pdf_scatter) <= 2 (the denominator is
-// >= 0.5 pdf_scatter > 0).
-template <bool ISO>
+// >= 0.5 pdf_scatter > 0).  RTW_F_ENV kernels: a sampled environment is light number n_lights -- the pick is over
+// n_lights + 1, the draws are the same four.
+template <bool ISO, uint32_t FEAT = 0>
 RTW_DHD bool mixture_scatter(const rtw_launch& L, const HitPrep& h, rtw_rng& rng, f3& dir, float& w) {
-    const uint32_t n = L.n_lights;
+    const uint32_t n = L.n_lights + env_lights<FEAT>(L);
     const float s = rnd(rng);
     if (s < 0.5f) {
         uint32_t k = (uint32_t)(rnd(rng) * (float)n);
         k = k < n - 1u ? k : n - 1u;
         const float a = rnd(rng);
         const float b = rnd(rng);
-        const rtw_dev_light lt = L.lights[k];
-        if (lt.kind == RTW_OBJ_SPHERE) {
+        bool env = false;
+        if constexpr ((FEAT & RTW_F_ENV) != 0) env = k >= L.n_lights;
+        rtw_dev_light lt{};
+        if (!env) lt = L.lights[k];
+        if (env) {
+            if constexpr ((FEAT & RTW_F_ENV) != 0) dir = env_sample(*rtw_env_of(L), a, b);
+        } else if (lt.kind == RTW_OBJ_SPHERE) {
             // uniform in the cone the sphere subtends: z = 1 - b (1 - cos(theta_max)) about w = unit(centre - p),
             // in the book's orthonormal basis ("The Rest of Your Life": helper axis, v = unit(w x helper), u = w x v)
             const f3 dc = ld3(lt.c) - h.p;
@@ -1545,7 +1640,7 @@ RTW_DHD bool mixture_scatter(const rtw_launch& L, const HitPrep& h, rtw_rng& rng
         ps = c > 0.0f ? RTW_DIV(c, kPi) : 0.0f;  // (a NaN cosine -- a zero direction -- ends the path too)
     }
     if (!(ps > 0.0f)) return false;
-    const float pl = light_pdf(L, h.p, dir);
+    const float pl = light_pdf<FEAT>(L, h.p, dir);
     w = RTW_DIV(ps, 0.5f * pl + 0.5f * ps);
     return true;
 }
@@ -1565,9 +1660,9 @@ RTW_DHD bool scatter_finish(const rtw_launch& L, const Ray& r, const HitPrep& h,
         f3 dir = h.normal + ruv;
         if (near_zero(dir)) dir = h.normal;
         if constexpr ((FEAT & RTW_F_PDF) != 0) {
-            if (L.n_lights) {
+            if (L.n_lights + env_lights<FEAT>(L)) {
                 float w;
-                if (!mixture_scatter<false>(L, h, rng, dir, w)) return false;
+                if (!mixture_scatter<false, FEAT & RTW_F_ENV>(L, h, rng, dir, w)) return false;
                 sc.d = dir;
                 att = texture_value<FEAT>(L, m.texture, h.uv, h.p) * splat(w);
                 return true;
@@ -1607,10 +1702,10 @@ RTW_DHD bool scatter_finish(const rtw_launch& L, const Ray& r, const HitPrep& h,
         }
         // RTW_MAT_ISOTROPIC (material.zig:139-143)
         if constexpr ((FEAT & RTW_F_PDF) != 0) {
-            if (L.n_lights) {
+            if (L.n_lights + env_lights<FEAT>(L)) {
                 f3 dir = ruv;
                 float w;
-                if (!mixture_scatter<true>(L, h, rng, dir, w)) return false;
+                if (!mixture_scatter<true, FEAT & RTW_F_ENV>(L, h, rng, dir, w)) return false;
                 sc.d = dir;
                 att = texture_value<FEAT>(L, m.texture, h.uv, h.p) * splat(w);
                 return true;
@@ -1666,7 +1761,7 @@ __host__ __device__ f3 sample_radiance(const float4* __restrict__ nodes, const r
         float t;
         const int hit = traverse<FEAT>(nodes, L, r, t, cnt, rng.s);
         if (hit < 0) {
-            acc = acc + thr * background(L, r);
+            acc = acc + thr * background<FEAT>(L, r);
             break;
         }
         f3 att;

@@ -434,7 +434,6 @@ void set_launch_knobs(rtw_ctx* ctx, const rtw_scene_desc* d, const rtw_tuning& t
     L.feat = ctx->feat;
     L.work_counter = ctx->d_work;
     L.shade_min = tu.mega_shade_min;
-    L.waves = tu.mega_waves;
     L.tile_order = tu.mega_tile_order ? 1u : 0u;
     // (an unfiltered variant measured +-0 on C2 and -20 % on C4: its codegen slowed the L1/L2 walk)
     L.fast_reject = tu.fast_reject ? 1u : 0u;
@@ -687,6 +686,7 @@ void rtw_scene_destroy(rtw_ctx* ctx) {
     if (ctx->d_tl) (void)hipFree(ctx->d_tl);
     if (ctx->d_lights) (void)hipFree(ctx->d_lights);
     if (ctx->d_vattrs) (void)hipFree(ctx->d_vattrs);
+    if (ctx->d_env) (void)hipFree(ctx->d_env);
     for (float4* p : ctx->d_dn)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -736,7 +736,198 @@ int rtw_scene_hash(rtw_ctx* ctx, uint64_t* out) {
             for (uint32_t x : w) mix(x);
         }
     }
+    // then the registered environment (none: the hash as it was): its digest covers map, scale, rotation and flags
+    if (ctx->env_hash) {
+        mix(0x52564E45u);  // "ENVR"
+        mix((uint32_t)ctx->env_hash);
+        mix((uint32_t)(ctx->env_hash >> 32));
+    }
     *out = h;
+    return RTW_OK;
+}
+
+int rtw_scene_set_environment(rtw_ctx* ctx, const rtw_environment* env) {
+#pragma STDC FP_CONTRACT OFF
+    if (!ctx) return fail(RTW_E_INVALID, "null ctx");
+    const bool host = ctx->device == RTW_DEVICE_CPU;
+    std::vector<float4> block;
+    std::vector<float> rgb;
+    uint64_t digest = 0;
+    char msg[240];
+    if (env) {
+        if (!env->rgb) return fail(RTW_E_INVALID, "rtw_scene_set_environment: null rgb");
+        const uint32_t W = env->width, H = env->height;
+        if (W == 0 || H == 0 || W > RTW_ENV_MAX_WIDTH || H > RTW_ENV_MAX_HEIGHT) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_environment: a map of %u x %u (1 x 1 up to %d x %d)", W, H,
+                          RTW_ENV_MAX_WIDTH, RTW_ENV_MAX_HEIGHT);
+            return fail(RTW_E_INVALID, msg);
+        }
+        for (int k = 0; k < 3; k++)
+            if (!(env->scale[k] >= 0.0f) || !std::isfinite(env->scale[k])) {
+                std::snprintf(msg, sizeof msg, "rtw_scene_set_environment: scale[%d] is negative or not finite", k);
+                return fail(RTW_E_INVALID, msg);
+            }
+        if (!std::isfinite(env->rotate_y)) return fail(RTW_E_INVALID, "rtw_scene_set_environment: rotate_y is not finite");
+        if (env->flags & ~(uint32_t)RTW_ENV_SAMPLE) {
+            std::snprintf(msg, sizeof msg, "rtw_scene_set_environment: unknown flag bits 0x%x", env->flags);
+            return fail(RTW_E_INVALID, msg);
+        }
+        const size_t n = (size_t)W * H;
+        rgb.assign(env->rgb, env->rgb + 3 * n);  // the one read of the caller's memory
+        for (size_t i = 0; i < 3 * n; i++)
+            if (!(rgb[i] >= 0.0f) || !std::isfinite(rgb[i])) {
+                std::snprintf(msg, sizeof msg, "rtw_scene_set_environment: texel (%zu, %zu) channel %zu is negative or "
+                              "not finite", (i / 3) % W, (i / 3) / W, i % 3);
+                return fail(RTW_E_INVALID, msg);
+            }
+        // the block: head (4 float4), texels, marginal, conditional (rtw_layout.h rtw_dev_env)
+        const size_t head = sizeof(rtw_dev_env) / 16, tab = (H + n + 3) / 4;
+        block.assign(head + n + tab, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+        float4* tex = block.data() + head;
+        float* marg = reinterpret_cast<float*>(tex + n);
+        float* cond = marg + H;
+        // radiance = scale * texel: one fp32 product per channel; a product that overflows is refused as a texel is
+        for (size_t i = 0; i < n; i++) {
+            tex[i] = make_float4(env->scale[0] * rgb[3 * i], env->scale[1] * rgb[3 * i + 1], env->scale[2] * rgb[3 * i + 2], 0.0f);
+            if (!std::isfinite(tex[i].x) || !std::isfinite(tex[i].y) || !std::isfinite(tex[i].z)) {
+                std::snprintf(msg, sizeof msg, "rtw_scene_set_environment: scale * texel (%zu, %zu) is not finite", i % W,
+                              i / W);
+                return fail(RTW_E_INVALID, msg);
+            }
+        }
+        // The sampling tables, in fp64, stored as fp32: w = lum(radiance) sin(pi (j + 0.5) / H); the conditional
+        // distribution of each row over its columns and the marginal one over the rows, cumulative, each divided
+        // by its total and its last entry set to exactly 1 (a row of no weight: all 1, never picked -- its marginal
+        // cell is empty); D = P_ij W H / (2 pi^2).
+        const double pi = 3.14159265358979323846;
+        std::vector<double> row_w(H, 0.0);
+        double total = 0.0;
+        for (uint32_t j = 0; j < H; j++) {
+            const double sn = std::sin(pi * ((double)j + 0.5) / (double)H);
+            double acc = 0.0;
+            for (uint32_t i = 0; i < W; i++) {
+                const float4 t = tex[(size_t)j * W + i];
+                acc += (0.2126 * (double)t.x + 0.7152 * (double)t.y + 0.0722 * (double)t.z) * sn;
+            }
+            row_w[j] = acc;
+            total += acc;
+        }
+        const bool sampled = (env->flags & RTW_ENV_SAMPLE) && total > 0.0 && std::isfinite(total);
+        if (sampled) {
+            const double dk = (double)W * (double)H / (2.0 * pi * pi);
+            double macc = 0.0;
+            for (uint32_t j = 0; j < H; j++) {
+                const double sn = std::sin(pi * ((double)j + 0.5) / (double)H);
+                double acc = 0.0;
+                for (uint32_t i = 0; i < W; i++) {
+                    float4& t = tex[(size_t)j * W + i];
+                    const double w = (0.2126 * (double)t.x + 0.7152 * (double)t.y + 0.0722 * (double)t.z) * sn;
+                    acc += w;
+                    cond[(size_t)j * W + i] = row_w[j] > 0.0 ? (float)(acc / row_w[j]) : 1.0f;
+                    t.w = (float)(w / total * dk);
+                }
+                cond[(size_t)j * W + W - 1] = 1.0f;
+                macc += row_w[j];
+                marg[j] = (float)(macc / total);
+            }
+            // rounding to fp32 may lift an entry onto 1 before the last row or column of weight: keep every entry
+            // below the last cell of weight strictly below 1, so that cell stays pickable
+            auto cap = [](float* c, uint32_t m, auto weight) {
+                uint32_t last = m - 1;
+                while (last > 0 && !(weight(last) > 0.0)) last--;
+                for (uint32_t k = 0; k < last; k++)
+                    if (c[k] >= 1.0f) c[k] = 0x1.fffffep-1f;
+                for (uint32_t k = last; k < m; k++) c[k] = 1.0f;
+            };
+            cap(marg, H, [&](uint32_t j) { return row_w[j]; });
+            for (uint32_t j = 0; j < H; j++)
+                if (row_w[j] > 0.0)
+                    cap(cond + (size_t)j * W, W, [&](uint32_t i) {
+                        const float4 t = tex[(size_t)j * W + i];
+                        return 0.2126 * (double)t.x + 0.7152 * (double)t.y + 0.0722 * (double)t.z;
+                    });
+        }
+        rtw_dev_env hd{};
+        hd.width = W;
+        hd.height = H;
+        {   // RotateY.init (objects.zig:352-355): degreesToRadians in fp32, then sin / cos, as rtw_bvh.hip takes them
+            const float pi32 = 3.1415926535897932385f;
+            const float radians = env->rotate_y * pi32 / 180.0f;
+            hd.sin_y = std::sin(radians);
+            hd.cos_y = std::cos(radians);
+        }
+        hd.sampled = sampled ? 1u : 0u;
+        hd.texels = tex;
+        hd.marginal = marg;
+        hd.conditional = cond;
+        std::memcpy(block.data(), &hd, sizeof hd);
+        // the digest: FNV-1a 64 of dimensions, scale, rotation, flags and the map as given; never 0
+        uint64_t h = 0xCBF29CE484222325ull;
+        auto mixb = [&h](const void* p, size_t nb) {
+            const uint8_t* b = static_cast<const uint8_t*>(p);
+            for (size_t i = 0; i < nb; i++) h = (h ^ b[i]) * 0x100000001B3ull;
+        };
+        mixb(&W, 4);
+        mixb(&H, 4);
+        mixb(env->scale, 12);
+        mixb(&env->rotate_y, 4);
+        mixb(&env->flags, 4);
+        mixb(rgb.data(), rgb.size() * 4);
+        digest = h ? h : 1;
+    }
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    rtw_launch base = ctx->base;
+    void* d_new = nullptr;
+    if (!host) {
+        HIP_TRY(hipSetDevice(ctx->device));
+        // a render left on a caller's stream (RTW_RENDER_NO_SYNC) may still read the old block
+        if (ctx->last_done) HIP_TRY(hipEventSynchronize(ctx->last_done));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (env) {
+            HIP_TRY(hipMalloc(&d_new, block.size() * 16));
+            // the device copy's head addresses the device copy's tables
+            std::vector<float4> headv(block.begin(), block.begin() + sizeof(rtw_dev_env) / 16);
+            rtw_dev_env hd;
+            std::memcpy(&hd, headv.data(), sizeof hd);
+            const char* hb = reinterpret_cast<const char*>(block.data());
+            char* db = static_cast<char*>(d_new);
+            hd.texels = reinterpret_cast<const float4*>(db + (reinterpret_cast<const char*>(hd.texels) - hb));
+            hd.marginal = reinterpret_cast<const float*>(db + (reinterpret_cast<const char*>(hd.marginal) - hb));
+            hd.conditional = reinterpret_cast<const float*>(db + (reinterpret_cast<const char*>(hd.conditional) - hb));
+            hipError_t e = hipMemcpy(d_new, block.data(), block.size() * 16, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy(d_new, &hd, sizeof hd, hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                (void)hipFree(d_new);
+                return rtw_hip_fail(e, "rtw_scene_set_environment: upload");
+            }
+        }
+    }
+    // (moving the vector keeps its storage: the head's host addresses stay valid)
+    const rtw_dev_env* addr = !env ? nullptr : host ? reinterpret_cast<const rtw_dev_env*>(block.data())
+                                                    : static_cast<const rtw_dev_env*>(d_new);
+    if (!rtw_env_set(base, addr)) {
+        if (d_new) (void)hipFree(d_new);
+        return fail(RTW_E_INVALID, "rtw_scene_set_environment: the block's address does not fit 48 bits");
+    }
+    if (ctx->d_env) (void)hipFree(ctx->d_env);
+    ctx->d_env = d_new;
+    ctx->env_block = std::move(block);
+    ctx->env_rgb = std::move(rgb);
+    ctx->env_given = env ? *env : rtw_environment{};
+    ctx->env_given.rgb = nullptr;
+    ctx->env_hash = digest;
+    // the persistent kernel's resident grid is its instantiation's
+    if (!host) ctx->grid = rtw_persistent_grid(rtw_feat_of(base), ctx->stats.n_nodes, base.use_lds != 0);
+    ctx->base = base;
+    return RTW_OK;
+}
+
+int rtw_scene_environment_get(rtw_ctx* ctx, rtw_environment* out, float* rgb, uint64_t cap_floats) {
+    if (!ctx) return fail(RTW_E_INVALID, "null ctx");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (out) *out = ctx->env_given;
+    if (rgb && !ctx->env_rgb.empty())
+        std::memcpy(rgb, ctx->env_rgb.data(), 4 * (size_t)std::min<uint64_t>(cap_floats, ctx->env_rgb.size()));
     return RTW_OK;
 }
 

@@ -67,8 +67,15 @@ struct rtw_launch {
     uint32_t* work_counter;      // zeroed before every launch
     uint32_t n_tiles_x, n_tiles;
     uint32_t shade_min;          // lanes that must be ready before a shading pass (<= 64)
-    uint32_t feat;               // RTW_F_* scene features (selects the kernel instantiation)
-    uint32_t waves;              // launch-bound variant (min waves per SIMD): 1, 6 or 8
+    // Two words no kernel reads (the host's dispatchers alone read `feat`; the second held a launch-bound variant
+    // nothing consults): the scene features in 12 bits, and beside them the address of the registered environment's
+    // block (rtw_dev_env, rtw_layout.h; rtw_scene_set_environment) in 48 -- every address a device or a host
+    // hands out fits --, 0 = none.  In place, so sizeof(rtw_launch) and every offset a kernel reads stay what they
+    // were (see vattrs below).  Read through rtw_env_of, by the RTW_F_ENV kernels only.
+    uint32_t feat : 12;          // RTW_F_* scene features up to RTW_F_TREE (selects the kernel instantiation)
+    uint32_t _spare : 4;
+    uint32_t env_hi : 16;        // bits 32 .. 47 of the environment block's address
+    uint32_t env_lo;             // bits 0 .. 31
     uint32_t tile_order;         // 1 = last tile row first (default), 0 = first row first
     uint32_t use_lds;            // 1 = stage the BVH in LDS when it fits (default), 0 = read nodes from L1/L2
     uint32_t fast_reject;        // 1 = exact sphere fast-reject filter (default), 0 = always the IEEE path
@@ -104,7 +111,7 @@ struct rtw_launch {
     const rtw_dev_light* lights; // n_lights records by kind: a quad's geometry is quads[lights[k].quad], a
                                  // sphere's centre and radius are in the record
 };
-static_assert(sizeof(rtw_launch) == 416 && offsetof(rtw_launch, vattrs) == 360 && offsetof(rtw_launch, perlin_lds) == 376 &&
+static_assert(sizeof(rtw_launch) == 416 && offsetof(rtw_launch, env_lo) == 328 && offsetof(rtw_launch, vattrs) == 360 && offsetof(rtw_launch, perlin_lds) == 376 &&
                   offsetof(rtw_launch, inodes) == 392 && offsetof(rtw_launch, lights) == 408,
               "rtw_launch keeps its size and the offsets its kernels read");
 
@@ -130,6 +137,10 @@ static_assert(sizeof(rtw_launch) == 416 && offsetof(rtw_launch, vattrs) == 360 &
 #define RTW_F_ATTR 512u     // vertex attributes are registered (rtw_launch.vattrs): a triangle's hit record takes its
                             // shading normal and (u, v) from them (quad_attr); only ever set on top of RTW_F_ALL |
                             // RTW_F_TREE [| RTW_F_PDF], by the dispatchers (rtw_feat_of), never stored in rtw_launch.feat
+#define RTW_F_ENV 1024u     // an environment is registered (rtw_env_of(L) != null): a miss looks the map up instead of
+                            // the camera's background, and with RTW_ENV_SAMPLE the map is one more light of the mixture
+                            // density; only ever set on top of RTW_F_ALL | RTW_F_TREE | RTW_F_PDF [| RTW_F_ATTR], by
+                            // the dispatchers (rtw_feat_of), never stored in rtw_launch.feat
 
 // max nodes staged in LDS by the persistent kernel (48 KiB)
 #define RTW_MEGA_LDS_NODES_MAX 1536
@@ -138,18 +149,32 @@ struct rtw_kernel_info {
     int blocks_per_cu;
     int n_cu;
 };
+// the registered environment's block, or null (host and device)
+__host__ __device__ inline const rtw_dev_env* rtw_env_of(const rtw_launch& L) {
+    return reinterpret_cast<const rtw_dev_env*>(((uint64_t)L.env_hi << 32) | (uint64_t)L.env_lo);
+}
+inline bool rtw_env_set(rtw_launch& L, const rtw_dev_env* e) {
+    const uint64_t a = reinterpret_cast<uint64_t>(e);
+    L.env_hi = (uint32_t)(a >> 32) & 0xFFFFu;
+    L.env_lo = (uint32_t)a;
+    return rtw_env_of(L) == e;  // false: an address above 2^48
+}
 // the features a launch's kernels are picked by: the scene's, | RTW_F_PDF with lights registered, | RTW_F_ATTR with
-// vertex attributes registered
+// vertex attributes registered, | RTW_F_ENV with an environment registered
 inline uint32_t rtw_feat_of(const rtw_launch& L) {
-    return L.feat | (L.n_lights ? RTW_F_PDF : 0u) | (L.vattrs ? RTW_F_ATTR : 0u);
+    return L.feat | (L.n_lights ? RTW_F_PDF : 0u) | (L.vattrs ? RTW_F_ATTR : 0u) | (rtw_env_of(L) ? RTW_F_ENV : 0u);
 }
 // What the registered features make of a feature set, the rule every dispatcher opens with (pick_feat below, the
 // wavefront's wf_pick_feat): vertex attributes run on top of every feature and the instance trees (a scene without
 // a tree runs them too: inst_hit_t falls back to the member loop), with or without the lights' mixture density;
 // lights on top of every feature; instance trees (inst_tree_t) likewise.  0: none of the three bits is set.
 // RTW_F_TREE is only ever set on top of RTW_F_ALL, so a dispatcher's "checker only" rule never sees it: testing
-// TREE before that rule (here) or after it picks the same class.
+// TREE before that rule (here) or after it picks the same class.  An environment runs on top of all of it, the
+// mixture density included (its kernels check n_lights, vattrs and the sample flag at run time as the RTW_F_PDF and
+// RTW_F_ATTR code does): two classes, with and without the vertex attributes, cover every combination -- a scene of
+// spheres alone too, whose 32-B node arrays (octant copies, hoisted leaves) the general walk reads.
 inline uint32_t rtw_feat_prefix(uint32_t f) {
+    if (f & RTW_F_ENV) return RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ENV | (f & RTW_F_ATTR);
     if (f & RTW_F_ATTR) return RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR | (f & RTW_F_PDF);
     if (f & RTW_F_PDF) return RTW_F_ALL | (f & RTW_F_TREE) | RTW_F_PDF;
     return (f & RTW_F_TREE) ? (RTW_F_ALL | RTW_F_TREE) : 0u;
@@ -171,7 +196,8 @@ struct RtwClasses {
 };
 using RtwObjectClasses =
     RtwClasses<RTW_F_ALL, RTW_F_ALL | RTW_F_TREE, RTW_F_ALL | RTW_F_PDF, RTW_F_ALL | RTW_F_TREE | RTW_F_PDF,
-               RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR, RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>;
+               RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR, RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR,
+               RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ENV, RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR | RTW_F_ENV>;
 using RtwSphereClasses = RtwClasses<0u, RTW_F_CHECKER>;
 // The classes of the first-hit kernels -- the guide buffers (rtw_denoise.hip) and the ray queries (rtw_query.hip),
 // where nothing scatters (RTW_F_PDF is irrelevant): every feature but the media (object_leaf gives a medium leaf
@@ -184,7 +210,17 @@ inline uint32_t rtw_first_hit_class(const rtw_launch& L) {
     if (f & RTW_F_ATTR) return kRtwFirstHitBase | RTW_F_TREE | RTW_F_ATTR;
     return (f & RTW_F_TREE) ? (kRtwFirstHitBase | RTW_F_TREE) : kRtwFirstHitBase;
 }
-// Calls f with the class of the features `feat` (rtw_feat_of): one of the six object classes, or with SPHERES
+// The guide kernels' classes (rtw_denoise.hip): the first-hit ones, and with an environment registered -- a miss's
+// albedo is its radiance -- those with the trees [and the attributes] | RTW_F_ENV.  (The ray queries keep
+// RtwFirstHitClasses: an environment is no hit.)
+using RtwGuideEnvClasses =
+    RtwClasses<kRtwFirstHitBase | RTW_F_TREE | RTW_F_ENV, kRtwFirstHitBase | RTW_F_TREE | RTW_F_ATTR | RTW_F_ENV>;
+inline uint32_t rtw_guide_class(const rtw_launch& L) {
+    const uint32_t f = rtw_feat_of(L);
+    if (f & RTW_F_ENV) return kRtwFirstHitBase | RTW_F_TREE | RTW_F_ENV | (f & RTW_F_ATTR);
+    return rtw_first_hit_class(L);
+}
+// Calls f with the class of the features `feat` (rtw_feat_of): one of the eight object classes, or with SPHERES
 // (the persistent kernel) also one of the two sphere-scene classes, which the other kernels run as RTW_F_ALL.
 template <bool SPHERES, typename F>
 void rtw_with_class(uint32_t feat, F&& f) {
@@ -408,6 +444,15 @@ struct rtw_ctx {
     std::vector<rtw_vertex_attr> vattr_set;
     std::vector<rtw_dev_vattr> vattrs_rec;
     rtw_dev_vattr* d_vattrs = nullptr;
+    // environment map (rtw_scene_set_environment): the block of rtw_layout.h's rtw_dev_env with host addresses
+    // (base's env words address it on a host context; rtw_debug_environment and the getter read it on both kinds)
+    // and its device copy (GPU context: one allocation per registration, freed at the next), the caller's record
+    // and map as given, and their digest (0: none; rtw_scene_hash, rtw_multi_create)
+    std::vector<float4> env_block;
+    void* d_env = nullptr;
+    rtw_environment env_given{};
+    std::vector<float> env_rgb;
+    uint64_t env_hash = 0;
     float box_pad = 0;             // absolute pad baked into the inner boxes (SAH trees), 0 = none
     float extent = 0;              // max |coordinate| over the scene's boxes
     // Concurrent callers (the reference's 8 RenderThreads call Camera.render at once, main.zig:314-326):

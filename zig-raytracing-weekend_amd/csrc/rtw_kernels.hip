@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256, WAVES) void render_persistent_v1(rtw_launch L)
             if (shading) {
                 bool cont = false;
                 if (hit == -1) {
-                    Ls = Ls + thr * background(L, ray);
+                    Ls = Ls + thr * background<FEAT>(L, ray);
                 } else if (hit >= 0) {
                     f3 att;
                     Ray sc;

@@ -80,6 +80,22 @@ struct rtw_dev_light {
 };
 static_assert(sizeof(rtw_dev_light) == 32, "light record must be 32 bytes");
 
+// 64 B: the head of a registered environment's block (rtw_scene_set_environment; RTW_F_ENV kernels), which one
+// allocation holds: this record, then width * height texels (rgb = scale * texel, w = D, the density weight
+// P_ij W H / (2 pi^2), 0 with sampling off), then the marginal distribution over the rows (height floats) and the
+// conditional ones over each row's columns (height * width floats), both cumulative with a last entry of exactly 1.
+// One 16-B load per miss; the two searches and the density read through L1/L2.
+struct alignas(16) rtw_dev_env {
+    const float4* texels;
+    const float* marginal;
+    const float* conditional;
+    uint32_t width, height;
+    float sin_y, cos_y;      // of rotate_y, as RotateY.init takes them
+    uint32_t sampled;        // RTW_ENV_SAMPLE and a positive total weight: the map is light n_lights of the mixture
+    uint32_t _p[5];
+};
+static_assert(sizeof(rtw_dev_env) == 64, "environment head must be 64 bytes");
+
 // 64 B: the per-vertex attributes of triangle quads[i] (rtw_scene_set_vertex_attrs), an array parallel to `quads`:
 // the fields of rtw_vertex_attr in its order -- four 16-B loads, taken only under `flags` (RTW_ATTR_*; 0: the quad
 // has none -- every parallelogram).  Corners in the order q, q + u, q + v; the normals are unit vectors (normalised

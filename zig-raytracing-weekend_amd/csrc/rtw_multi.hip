@@ -207,15 +207,17 @@ int check_args(rtw_multi* m, const rtw_camera* cam, uint32_t rpb, uint32_t s0, u
     return RTW_OK;
 }
 
-// a context's registrations, copied under its lock (rtw_scene_set_lights / rtw_scene_set_vertex_attrs write there)
+// a context's registrations, copied under its lock (rtw_scene_set_lights / rtw_scene_set_vertex_attrs /
+// rtw_scene_set_environment write there)
 struct Registered {
     std::vector<rtw_object> lights;
     std::vector<uint32_t> quads;
     std::vector<rtw_vertex_attr> attrs;
+    uint64_t env_hash;  // rtw_scene_set_environment: 0 = none, else the digest of map, scale, rotation and flags
 };
 Registered registered(rtw_ctx* ctx) {
     std::lock_guard<std::mutex> lock(ctx->mu);
-    return {ctx->lights, ctx->vattr_quads, ctx->vattr_set};
+    return {ctx->lights, ctx->vattr_quads, ctx->vattr_set, ctx->env_hash};
 }
 
 }  // namespace
@@ -253,6 +255,11 @@ int rtw_multi_create(rtw_ctx* const* ctxs, uint32_t n, rtw_multi** out) {
             delete m;
             return mfail(RTW_E_INVALID,
                          "the contexts' vertex attributes differ (rtw_scene_set_vertex_attrs on each of them)");
+        }
+        // ... and the same environment
+        if (a.env_hash != b.env_hash) {
+            delete m;
+            return mfail(RTW_E_INVALID, "the contexts' environments differ (rtw_scene_set_environment on each of them)");
         }
         m->ctx.push_back(ctxs[k]);
         m->dev.push_back(ctxs[k]->device);

@@ -1162,7 +1162,7 @@ __device__ __forceinline__ void wf_shade_body(const rtw_launch& L, const rtw_wf&
                     rng.s = rs;
                 }
                 if (hit < 0) {
-                    acc = acc + thr * background(L, r);
+                    acc = acc + thr * background<FEAT>(L, r);
                 } else {
                     if constexpr ((FEAT & (RTW_F_GEOM | RTW_F_MEDIUM)) == 0) {
                         // sphere scenes: the split form of the fused step (hit record, then one
@@ -1315,7 +1315,7 @@ __device__ __forceinline__ void wf_tail_body(const rtw_launch& L, const rtw_wf& 
                 depth = fbits(p1.w);
             }
             if (hit < 0) {
-                acc = acc + thr * background(L, r);
+                acc = acc + thr * background<FEAT>(L, r);
             } else if constexpr ((FEAT & ~RTW_F_CHECKER) == 0) {
                 // untextured static sphere scenes: the fused step's split form (C2 tail -10 %, C4 -5 % over the
                 // nested form; the textured C5 tail +5 %: nested form there), in the fused step's order -- the
@@ -1604,7 +1604,7 @@ __device__ __forceinline__ void wf_step_body(const rtw_launch& L, const rtw_wf& 
                 if constexpr (CNT != 0) cnt.rays++;
                 late_rest();
                 if (hit < 0) {
-                    acc = acc + thr * background(L, r);
+                    acc = acc + thr * background<FEAT>(L, r);
                 } else {
                     hhit = hit;
                     ht = t;
@@ -1648,7 +1648,7 @@ __device__ __forceinline__ void wf_step_body(const rtw_launch& L, const rtw_wf& 
             wf_reject3(need_uv, rng, uv3);
             if (live) {
                 if (hit < 0) {
-                    acc = acc + thr * background(L, r);
+                    acc = acc + thr * background<FEAT>(L, r);
                 } else {
                     const HitPrep hp = hit_prep<FEAT>(L.nodes, L, r, hit, t);
                     const f3 ruv = need_uv ? unit_vector(mk(uv3[0], uv3[1], uv3[2])) : mk(0, 0, 0);

@@ -1,6 +1,6 @@
 // rtw_wavefront_dispatch.h -- the host side of the wavefront path: grid sizes, the staging plan, the launches of one
 // batch and the scene-class tables.  Included as the last line of rtw_wavefront.hip (it names the kernel templates),
-// so once per translation unit: rtw_wavefront.hip itself and the three RTW_WF_*_TU wrappers.
+// so once per translation unit: rtw_wavefront.hip itself and the four RTW_WF_*_TU wrappers.
 #pragma once
 #include <map>
 #include <mutex>
@@ -423,8 +423,13 @@ struct WfClasses {
 //   WF_TU_LIGHTS   contexts with registered lights (rtw_feat_of: RTW_F_PDF; rtw_wavefront_lights.hip)
 //   WF_TU_ATTRS    contexts with registered vertex attributes (RTW_F_ATTR; rtw_wavefront_attrs.hip)
 //   WF_TU_MAIN     every other class (rtw_wavefront.hip)
-enum { WF_TU_MAIN, WF_TU_SPHERES, WF_TU_LIGHTS, WF_TU_ATTRS };
-#if defined(RTW_WF_ATTRS_TU)
+//   WF_TU_ENV      contexts with a registered environment (RTW_F_ENV; rtw_wavefront_env.hip)
+enum { WF_TU_MAIN, WF_TU_SPHERES, WF_TU_LIGHTS, WF_TU_ATTRS, WF_TU_ENV };
+#if defined(RTW_WF_ENV_TU)
+constexpr int WF_TU = WF_TU_ENV;
+using WfUnit = WfClasses<RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ENV,
+                         RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR | RTW_F_ENV>;
+#elif defined(RTW_WF_ATTRS_TU)
 constexpr int WF_TU = WF_TU_ATTRS;
 using WfUnit = WfClasses<RTW_F_ALL | RTW_F_TREE | RTW_F_ATTR, RTW_F_ALL | RTW_F_TREE | RTW_F_PDF | RTW_F_ATTR>;
 #elif defined(RTW_WF_LIGHTS_TU)
@@ -450,7 +455,7 @@ uint32_t rtw_wf_unit_max_waves(int n_cu);
     bool rtw_wf_unit_run<TU>(uint32_t, const rtw_launch&, const rtw_wf&, hipStream_t, int, rtw_timer*);     \
     template <>                                                                                             \
     uint32_t rtw_wf_unit_max_waves<TU>(int);
-RTW_WF_UNIT(WF_TU_MAIN) RTW_WF_UNIT(WF_TU_SPHERES) RTW_WF_UNIT(WF_TU_LIGHTS) RTW_WF_UNIT(WF_TU_ATTRS)
+RTW_WF_UNIT(WF_TU_MAIN) RTW_WF_UNIT(WF_TU_SPHERES) RTW_WF_UNIT(WF_TU_LIGHTS) RTW_WF_UNIT(WF_TU_ATTRS) RTW_WF_UNIT(WF_TU_ENV)
 #undef RTW_WF_UNIT
 
 template <>
@@ -463,7 +468,7 @@ uint32_t rtw_wf_unit_max_waves<WF_TU>(int n_cu) {
     return WfUnit::max_waves(n_cu);
 }
 
-#if !defined(RTW_WF_ATTRS_TU) && !defined(RTW_WF_LIGHTS_TU) && !defined(RTW_WF_SPHERES_TU)
+#if !defined(RTW_WF_ENV_TU) && !defined(RTW_WF_ATTRS_TU) && !defined(RTW_WF_LIGHTS_TU) && !defined(RTW_WF_SPHERES_TU)
 template <int... TU>
 struct WfUnits {
     static bool run(uint32_t feat, const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, rtw_timer* T) {
@@ -471,7 +476,7 @@ struct WfUnits {
     }
     static uint32_t max_waves(int n_cu) { return std::max({rtw_wf_unit_max_waves<TU>(n_cu)...}); }
 };
-using WfAllUnits = WfUnits<WF_TU_MAIN, WF_TU_SPHERES, WF_TU_LIGHTS, WF_TU_ATTRS>;
+using WfAllUnits = WfUnits<WF_TU_MAIN, WF_TU_SPHERES, WF_TU_LIGHTS, WF_TU_ATTRS, WF_TU_ENV>;
 
 void rtw_wavefront_batch(const rtw_launch& L, const rtw_wf& W, void* stream, int n_cu, rtw_timer* T) {
     (void)WfAllUnits::run(wf_pick_feat(rtw_feat_of(L)), L, W, (hipStream_t)stream, n_cu, T);

@@ -434,6 +434,95 @@ def createBox(a, b, mat: Material) -> HittableList:
     return sides
 
 
+class Environment:
+    """An environment map (rtw_environment): an equirectangular image of linear radiance, float32 (H, W, 3), row 0
+    at +y, looked up by the direction of a ray that leaves the scene (sphere_uv's mapping, nearest texel).
+    radiance = scale * texel; rotate_y turns the map about y (degrees); sample=True makes the map one more light
+    of the mixture density diffuse scatter draws from (RTW_ENV_SAMPLE), so a small bright sun converges."""
+
+    def __init__(self, rgb, scale=(1.0, 1.0, 1.0), rotate_y: float = 0.0, sample: bool = True):
+        a = np.ascontiguousarray(rgb, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("Environment: rgb is not (height, width, 3)")
+        self.rgb = a
+        self.scale = tuple(float(x) for x in np.asarray(scale, np.float32).reshape(3))
+        self.rotate_y = float(rotate_y)
+        self.sample = bool(sample)
+
+    @property
+    def width(self) -> int:
+        return self.rgb.shape[1]
+
+    @property
+    def height(self) -> int:
+        return self.rgb.shape[0]
+
+    def record(self) -> "_abi.RtwEnvironment":
+        """The rtw_environment of this map (it addresses self.rgb: keep self alive across the call)."""
+        r = _abi.RtwEnvironment()
+        r.rgb = self.rgb.ctypes.data
+        r.width, r.height = self.width, self.height
+        r.scale[:] = list(self.scale)
+        r.rotate_y = self.rotate_y
+        r.flags = _abi.RTW_ENV_SAMPLE if self.sample else 0
+        return r
+
+    @staticmethod
+    def load_hdr(path, **kw) -> "Environment":
+        """A Radiance RGBE (.hdr) file as an Environment: flat or new-style run-length-encoded scanlines,
+        orientation "-Y h +X w" only.  A pixel (r, g, b, e) is (r, g, b) * 2^(e - 136), and 0 where e = 0."""
+        with open(path, "rb") as f:
+            data = f.read()
+        if not (data.startswith(b"#?RADIANCE") or data.startswith(b"#?RGBE")):
+            raise ValueError(f"{path}: not a Radiance RGBE file")
+        end = data.find(b"\n\n")
+        if end < 0:
+            raise ValueError(f"{path}: no end of header")
+        header = data[:end].split(b"\n")
+        if not any(ln.strip() == b"FORMAT=32-bit_rle_rgbe" for ln in header):
+            raise ValueError(f"{path}: FORMAT is not 32-bit_rle_rgbe")
+        eol = data.find(b"\n", end + 2)
+        res = data[end + 2:eol].split()
+        if len(res) != 4 or res[0] != b"-Y" or res[2] != b"+X":
+            raise ValueError(f"{path}: orientation {data[end + 2:eol]!r} (only '-Y h +X w' is read)")
+        h, w = int(res[1]), int(res[3])
+        raw = np.frombuffer(data, np.uint8, offset=eol + 1)
+        px = np.zeros((h, w, 4), np.uint8)
+        pos = 0
+        for y in range(h):
+            rle = 8 <= w < 32768 and pos + 4 <= len(raw) and raw[pos] == 2 and raw[pos + 1] == 2 and \
+                (int(raw[pos + 2]) << 8 | int(raw[pos + 3])) == w
+            if not rle:   # a flat scanline
+                if pos + 4 * w > len(raw):
+                    raise ValueError(f"{path}: truncated at scanline {y}")
+                px[y] = raw[pos:pos + 4 * w].reshape(w, 4)
+                pos += 4 * w
+                continue
+            pos += 4
+            for c in range(4):
+                x = 0
+                while x < w:
+                    if pos >= len(raw):
+                        raise ValueError(f"{path}: truncated at scanline {y}")
+                    n = int(raw[pos])
+                    pos += 1
+                    if n > 128:   # a run
+                        n -= 128
+                        if n == 0 or x + n > w or pos >= len(raw):
+                            raise ValueError(f"{path}: bad run at scanline {y}")
+                        px[y, x:x + n, c] = raw[pos]
+                        pos += 1
+                    else:         # literals
+                        if n == 0 or x + n > w or pos + n > len(raw):
+                            raise ValueError(f"{path}: bad literal count at scanline {y}")
+                        px[y, x:x + n, c] = raw[pos:pos + n]
+                        pos += n
+                    x += n
+        e = px[..., 3].astype(np.int32)
+        f = np.where(e > 0, np.ldexp(np.float32(1.0), e - 136), np.float32(0.0)).astype(np.float32)
+        return Environment(px[..., :3].astype(np.float32) * f[..., None], **kw)
+
+
 @dataclass
 class SceneArrays:
     """The neutral scene description handed across the C ABI."""
@@ -454,6 +543,7 @@ class SceneArrays:
     # (quad indices u4, VERTEX_ATTR_DT records) of the triangles with per-vertex normals / uvs, which World
     # registers (rtw_scene_set_vertex_attrs); None = none
     vertex_attrs: Optional[tuple] = None
+    environment: Optional["Environment"] = None   # World registers it (rtw_scene_set_environment); None = none
 
     def desc(self):
         """Build an RtwSceneDesc (keeps the ctypes image array alive on self)."""
@@ -482,9 +572,12 @@ class SceneArrays:
         return d
 
 
-def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None, lights=None) -> SceneArrays:
+def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None, lights=None,
+            environment: Optional["Environment"] = None) -> SceneArrays:
     """world_objects -> C-ABI records.  bvh_mode: RTW_BVH_SAH (default, fastest) or
     RTW_BVH_REFERENCE (the reference's random-axis median tree, seeded by bvh_seed).
+
+    environment: an Environment the World registers (rtw_scene_set_environment), carried on the arrays as given.
 
     lights: the quads and spheres diffuse scatter samples towards (rtw_scene_set_lights) -- None = none,
     "emissive" = every top-level Quad whose material is a DiffuseLight, "emissive+spheres" = those, then
@@ -645,7 +738,7 @@ def flatten(objects: Sequence, bvh_seed: int = 0, bvh_mode: Optional[int] = None
                        objects=None if only_spheres else arr(objs, _abi.OBJECT_DT),
                        lights=None if light_refs is None else arr(light_refs, _abi.OBJECT_DT),
                        vertex_attrs=(np.array(attr_quads, np.uint32), arr(attr_recs, _abi.VERTEX_ATTR_DT))
-                       if attr_quads else None)
+                       if attr_quads else None, environment=environment)
 
 
 def flatten_bvh(arrays: SceneArrays) -> np.ndarray:
@@ -684,6 +777,8 @@ class World:
                 self.set_lights(arrays.lights)
             if arrays.vertex_attrs is not None and len(arrays.vertex_attrs[0]):
                 self.set_vertex_attrs(*arrays.vertex_attrs)
+            if arrays.environment is not None:
+                self.set_environment(arrays.environment)
         except Exception:
             self.close()
             raise
@@ -728,6 +823,49 @@ class World:
         if n.value:
             _abi.check(f(self.handle, q.ctypes.data, a.ctypes.data, n.value, C.byref(n)), "rtw_scene_vertex_attrs_get")
         return q, a
+
+    def set_environment(self, env: Optional["Environment"]) -> None:
+        """rtw_scene_set_environment: the radiance a ray that leaves the scene collects -- an Environment, or None
+        to clear (the world then renders exactly as one never given any).  The map is copied at the call.  Must not
+        race a render on this world."""
+        f = _abi.lib().rtw_scene_set_environment
+        if env is None:
+            _abi.check(f(self.handle, None), "rtw_scene_set_environment")
+            return
+        rec = env.record()
+        _abi.check(f(self.handle, C.byref(rec)), "rtw_scene_set_environment")
+
+    def environment(self) -> Optional["Environment"]:
+        """The registered environment (rtw_scene_environment_get) as given, or None."""
+        f = _abi.lib().rtw_scene_environment_get
+        rec = _abi.RtwEnvironment()
+        _abi.check(f(self.handle, C.byref(rec), None, 0), "rtw_scene_environment_get")
+        if rec.width == 0:
+            return None
+        rgb = np.zeros((rec.height, rec.width, 3), np.float32)
+        _abi.check(f(self.handle, C.byref(rec), rgb.ctypes.data, rgb.size), "rtw_scene_environment_get")
+        return Environment(rgb, tuple(rec.scale), rec.rotate_y, bool(rec.flags & _abi.RTW_ENV_SAMPLE))
+
+    def debug_environment(self, dirs=None, draws=None) -> dict:
+        """rtw_debug_environment: the device's environment functions on the host.  dirs (N, 3) gives `radiance`
+        (N, 3), `pdf` (N,) -- the density of the map's own sampler, D / sin(theta), 0 with sampling off -- and
+        `texel` (N,), row * width + column; draws (N, 2) = (a, b) gives `sampled_dir` (N, 3)."""
+        d = None if dirs is None else np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        u = None if draws is None else np.ascontiguousarray(draws, np.float32).reshape(-1, 2)
+        if d is not None and u is not None and len(d) != len(u):
+            raise ValueError("debug_environment: as many draws as directions")
+        n = len(d) if d is not None else len(u) if u is not None else 0
+        out = {}
+        if d is not None:
+            out = {"radiance": np.zeros((n, 3), np.float32), "pdf": np.zeros(n, np.float32),
+                   "texel": np.zeros(n, np.uint32)}
+        if u is not None:
+            out["sampled_dir"] = np.zeros((n, 3), np.float32)
+        p = _abi.ptr
+        _abi.check(_abi.lib().rtw_debug_environment(self.handle, n, p(d), p(u), p(out.get("radiance")),
+                                                    p(out.get("pdf")), p(out.get("sampled_dir")), p(out.get("texel"))),
+                   "rtw_debug_environment")
+        return out
 
     def render_guides(self, cam) -> tuple:
         """rtw_render_guides: the first-hit guide buffers of the camera's frame, (albedo, normal_depth), each a

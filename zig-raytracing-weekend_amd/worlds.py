@@ -296,6 +296,35 @@ def cornell_mesh(level: int = 2, analytic: bool = False, smooth: bool = False) -
     return objs
 
 
+def env_directions(width: int, height: int, sub: int = 1) -> np.ndarray:
+    """Unit directions (float64, (height * sub, width * sub, 3)) of an equirectangular map's texels, `sub` x `sub`
+    regular sub-samples per texel: row 0 at +y, (u, v) = sphere_uv's, i.e. the inverse of the library's lookup --
+    theta = pi (1 - (j + .5) / H), phi = 2 pi (i + .5) / W, d = (-sin(theta) cos(phi), -cos(theta), sin(theta) sin(phi))."""
+    hh, ww = height * sub, width * sub
+    theta = np.pi * (1.0 - (np.arange(hh) + 0.5) / hh)[:, None]
+    phi = 2.0 * np.pi * ((np.arange(ww) + 0.5) / ww)[None, :]
+    st = np.sin(theta)
+    return np.stack([-st * np.cos(phi), np.broadcast_to(-np.cos(theta), (hh, ww)), st * np.sin(phi)], axis=-1)
+
+
+def sky_sun(width: int = 512, height: int = 256, sun_dir=(0.3, 0.8, 0.5), sun_radiance=5000.0,
+            sun_half_angle: float = 2.0, zenith=(0.25, 0.45, 0.9), horizon=(0.8, 0.85, 0.9)) -> np.ndarray:
+    """A procedural HDR sky for Environment: float32 (height, width, 3) linear radiance, row 0 at +y.  The sky
+    blends horizon -> zenith by the direction's height (the horizon colour below it); a sun of angular radius
+    sun_half_angle (degrees) about sun_dir adds sun_radiance (a scalar or rgb) times the fraction of the texel it
+    covers (4 x 4 sub-samples), so a sun smaller than a texel keeps its energy."""
+    sub = 4
+    d = env_directions(width, height, sub)
+    s = np.asarray(sun_dir, np.float64)
+    s = s / np.linalg.norm(s)
+    inside = (d @ s >= np.cos(np.radians(sun_half_angle))).astype(np.float64)
+    cover = inside.reshape(height, sub, width, sub).mean(axis=(1, 3))
+    up = np.clip(env_directions(width, height)[..., 1], 0.0, 1.0)[..., None]
+    sky = (1.0 - up) * np.asarray(horizon, np.float64) + up * np.asarray(zenith, np.float64)
+    sun = np.broadcast_to(np.asarray(sun_radiance, np.float64), (3,))
+    return (sky + cover[..., None] * sun).astype(np.float32)
+
+
 def next_week_world(seed: int = 0, boxes_per_side: int = 20, cluster: int = 1000,
                     images: Optional[Sequence[Image]] = None) -> list:
     """The final scene of *Ray Tracing: The Next Week* (not in the reference's main.zig: "Part 2" is an open
