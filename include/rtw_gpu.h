@@ -720,8 +720,9 @@ int rtw_debug_environment(rtw_ctx* ctx, uint32_t n, const float* dirs, const flo
  * out may alias accum; albedo may be NULL without DEMODULATE.  The two intermediate images belong to the context
  * and grow on demand; the calls take the context lock as renders do.  RTW_E_INVALID with a message, out untouched:
  * passes outside 1 .. RTW_DENOISE_MAX_PASSES, a negative or non-finite sigma, unknown flag bits, width * height == 0
- * (or beyond 2^32 - 1), a null required pointer, rtw_denoise_device on a host context.  Out of scope: variance-guided
- * or temporal filtering, a sharded multi-GPU filter (filter device 0's gathered frame), a pixel sub-range.
+ * (or beyond 2^32 - 1), a null required pointer, rtw_denoise_device on a host context.  Out of scope: temporal
+ * filtering, a sharded multi-GPU filter (filter device 0's gathered frame), a pixel sub-range.  (The variance-guided
+ * filter is rtw_denoise_guided, in the block after this one.)
  * ------------------------------------------------------------------------- */
 #define RTW_DENOISE_MAX_PASSES 8
 enum { RTW_DENOISE_DEMODULATE = 1u };
@@ -746,6 +747,76 @@ int rtw_denoise_device(rtw_ctx* ctx, uint32_t width, uint32_t height, const floa
                        uint32_t flags);
 /* Host-only: out[i] = e(x[i]) = exp(-x[i]), the filter's edge-stopping function (rtw_expneg, the device's code). */
 int rtw_debug_expneg(uint32_t n, const float* x, float* out);
+
+/* ---------------------------------------------------------------------------
+ * Noise estimates and the variance-guided filter: a running per-pixel estimate of the variance of luminance, a
+ * noise measure on it (a viewer's stop criterion, a sampler's map) and SVGF's spatial filter (Schied et al. 2017):
+ * the a-trous filter above with its colour term measured in standard deviations.  A caller detects the capability by
+ * the presence of these symbols (the ABI version and every struct above are those of ABI 8).  Kernels of their own:
+ * no render and no rtw_denoise result changes by a bit.  All in fp32, every operation rounded singly in the
+ * association written (nothing contracted), one function for the host and the device: they agree bit for bit.
+ * DESIGN.md §Noise estimates and the guided filter.
+ *
+ * Moments.  `moments` is the caller's: two float4[W*H] planes, one after the other -- plane 0 the accumulator as of
+ * the last update, plane 1 (mean, M2, n, sw) of the per-batch mean luminance.  All zeros is the reset state (a caller
+ * that scrubs its accumulator zeroes the moments).  rtw_moments_update, per pixel, a = accum, p = plane 0:
+ *   k = a.w - p.w;  unless k > 0 neither plane changes
+ *   inv = 1 / k;  d = (a.rgb - p.rgb) inv;  y = (0.2126 d.r + 0.7152 d.g) + 0.0722 d.b
+ *   y not finite: plane 0 = a, plane 1 unchanged;  otherwise (West's weighted update)
+ *   sw' = sw + k;  e = y - mean;  mean' = mean + e (k / sw');  M2' = M2 + (k e) (y - mean');  n' = n + 1;  plane 0 = a
+ * It works after any render call -- any pixel range, chunk, shard, gather or resumed checkpoint -- and takes what it
+ * finds at the first update as one batch.  Derived: for n >= 2, s2 = M2 / (n - 1) is the per-sample variance of
+ * luminance (unbiased for batches of unequal size) and v = s2 / sw the variance of the pixel's mean, a v that is not
+ * > 0 counting as 0; for n < 2 the variance is unknown.
+ *
+ * Noise estimate.  err = sqrt(v) / (|mean| + floor): +inf where the variance is unknown (the pixel needs more
+ * samples), 0 where v = 0 whatever the divisor.  err (W*H) and tile_max (ceil(W/8) * ceil(H/8), the maximum over each
+ * 8 x 8 pixel tile, rows of tiles in image order) may be NULL.  The summary: over = pixels with err > threshold,
+ * known = pixels with n >= 2, max_err = the largest finite err (0: none).  Maxima and integer counts only, so the
+ * backends agree exactly.  RTW_E_INVALID: a negative or non-finite floor or threshold.
+ *
+ * Guided filter.  rtw_denoise's arithmetic (pre-pass, taps, skipping, h, e, sums, the wsum = 0 rule, last pass) with
+ * params->sigma_color read as sl, in standard deviations, the same in every pass, and:
+ *   pre-pass   also a variance plane: v as above, -1 where unknown;  with DEMODULATE  v / (la la),
+ *              la = (0.2126 a.r + 0.7152 a.g) + 0.0722 a.b of a = max(albedo, 2^-8)
+ *   pass i     vbar = (sum of (g[dx] g[dy]) v_q) / (sum of g[dx] g[dy]), g = {1/4, 1/2, 1/4}, over the 3 x 3 taps at
+ *              spacing 1 (dy outer, dx inner) that are on the image, have the centre's hit state, a finite colour and
+ *              v_q >= 0.  kl = 1 / (sl sqrt(vbar) + 2^-20); the colour term is off for the pixel with no such tap,
+ *              with sl = 0 or where the centre's colour is not finite.  Per tap of the 5 x 5 at spacing 2^i:
+ *                tl = |Y_q - Y_p| kl,  Y = (0.2126 c.r + 0.7152 c.g) + 0.0722 c.b of the plane's colour
+ *                x = (tl + tn) + tz;  weight = (h[dx] h[dy]) e(x)
+ *              v' = (sum of (weight weight) max(v_q, 0)) / (wsum wsum), in tap order; the pixel's own v where
+ *              wsum = 0; -1 through every pass where the centre's variance is unknown
+ *   last pass  out as rtw_denoise;  variance_out (W*H floats, may be NULL) = v', with DEMODULATE v' (la la), -1 where
+ *              unknown: the variance of the filtered mean luminance
+ * out may alias accum.  Refusals are rtw_denoise's, plus a null moments; each leaves every output untouched.  The
+ * device forms take device buffers of a GPU context (the summary too), are enqueued on `stream` (NULL: the
+ * context's) and take flags RTW_RENDER_NO_SYNC; the host-buffer forms serve both kinds of context.  Out of scope:
+ * non-uniform sample counts, per-channel variance, temporal accumulation, moments in checkpoints, a sharded
+ * multi-GPU estimate or filter, a pixel sub-range.
+ * ------------------------------------------------------------------------- */
+typedef struct rtw_noise_summary {       /* 24 bytes */
+    uint64_t over, known;
+    float max_err;
+    uint32_t _pad;
+} rtw_noise_summary;
+int rtw_moments_update(rtw_ctx* ctx, uint32_t width, uint32_t height, const float* accum, float* moments);
+int rtw_moments_update_device(rtw_ctx* ctx, uint32_t width, uint32_t height, const float* d_accum, float* d_moments,
+                              void* stream, uint32_t flags);
+int rtw_noise_estimate(rtw_ctx* ctx, uint32_t width, uint32_t height, const float* moments, float floor,
+                       float threshold, float* err, float* tile_max, rtw_noise_summary* out);
+int rtw_noise_estimate_device(rtw_ctx* ctx, uint32_t width, uint32_t height, const float* d_moments, float floor,
+                              float threshold, float* d_err, float* d_tile_max, rtw_noise_summary* d_out, void* stream,
+                              uint32_t flags);
+/* The shipped parameters: the winner of the grid search recorded in profiles/denoise_guided/defaults.json. */
+void rtw_denoise_guided_defaults(rtw_denoise_params* p);
+int rtw_denoise_guided(rtw_ctx* ctx, uint32_t width, uint32_t height, const float* accum, const float* moments,
+                       const float* albedo, const float* normal_depth, const rtw_denoise_params* params, float* out,
+                       float* variance_out);
+int rtw_denoise_guided_device(rtw_ctx* ctx, uint32_t width, uint32_t height, const float* d_accum,
+                              const float* d_moments, const float* d_albedo, const float* d_normal_depth,
+                              const rtw_denoise_params* params, float* d_out, float* d_variance_out, void* stream,
+                              uint32_t flags);
 
 /* ---------------------------------------------------------------------------
  * Ray queries: the closest hit, or whether anything is hit, for rays the caller supplies -- picking (the object

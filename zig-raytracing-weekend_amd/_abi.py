@@ -189,10 +189,9 @@ class RtwDenoiseParams(C.Structure):
                 ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("_pad", C.c_float * 3)]
 
 
-def denoise_params(**fields) -> RtwDenoiseParams:
-    """rtw_denoise_defaults() with `fields` overridden; demodulate=True / False sets or clears the flag bit."""
+def _denoise_params(defaults, fields) -> RtwDenoiseParams:
     p = RtwDenoiseParams()
-    lib().rtw_denoise_defaults(C.byref(p))
+    defaults(C.byref(p))
     demod = fields.pop("demodulate", None)
     for k, v in fields.items():
         if k.startswith("_") or not hasattr(p, k):
@@ -201,6 +200,21 @@ def denoise_params(**fields) -> RtwDenoiseParams:
     if demod is not None:
         p.flags = (p.flags | RTW_DENOISE_DEMODULATE) if demod else (p.flags & ~RTW_DENOISE_DEMODULATE)
     return p
+
+
+def denoise_params(**fields) -> RtwDenoiseParams:
+    """rtw_denoise_defaults() with `fields` overridden; demodulate=True / False sets or clears the flag bit."""
+    return _denoise_params(lib().rtw_denoise_defaults, fields)
+
+
+def denoise_guided_params(**fields) -> RtwDenoiseParams:
+    """rtw_denoise_guided_defaults() with `fields` overridden, as denoise_params (sigma_color: standard deviations)."""
+    return _denoise_params(lib().rtw_denoise_guided_defaults, fields)
+
+
+class RtwNoiseSummary(C.Structure):
+    # rtw_noise_summary (24 bytes): pixels over the threshold, pixels with a known variance, the largest finite error
+    _fields_ = [("over", C.c_uint64), ("known", C.c_uint64), ("max_err", C.c_float), ("_pad", C.c_uint32)]
 
 
 class RtwEnvironment(C.Structure):
@@ -329,6 +343,19 @@ SIGNATURES = {
     "rtw_denoise_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.POINTER(RtwDenoiseParams), C.c_void_p, C.c_void_p, C.c_uint32]),
     "rtw_debug_expneg": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rtw_moments_update": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rtw_moments_update_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_uint32]),
+    "rtw_noise_estimate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
+                                     C.c_void_p, C.POINTER(RtwNoiseSummary)]),
+    "rtw_noise_estimate_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rtw_denoise_guided_defaults": (None, [C.POINTER(RtwDenoiseParams)]),
+    "rtw_denoise_guided": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(RtwDenoiseParams), C.c_void_p, C.c_void_p]),
+    "rtw_denoise_guided_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.POINTER(RtwDenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_uint32]),
     "rtw_trace_rays": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "rtw_trace_rays_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "rtw_occluded": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -37,10 +37,13 @@ class SharedStateImageWriter:
         self.buffer = np.zeros((n, 4), np.float32)
         self.buffer[:, 3] = 1.0                      # init / scrub: {0,0,0,1} (camera.zig:34-45)
         self.texture_buffer = np.zeros((n, 4), np.uint8)
+        self.moments: Optional[np.ndarray] = None    # rtw_moments_update's two planes (RayTraceState.moments)
 
     def scrub(self):
         self.buffer[:] = 0.0
         self.buffer[:, 3] = 1.0
+        if self.moments is not None:
+            self.moments[:] = 0.0
 
     def update_texture(self, begin: int = 0, end: Optional[int] = None):
         """toGamma2 texel update of writeColor (camera.zig:58-65) for [begin, end)."""
@@ -181,17 +184,36 @@ class RayTraceState:
         """Samples per pixel already in the buffer (writeColor stores the count in .w)."""
         return int(self.writer.buffer[:, 3].max()) if self.writer.buffer.size else 0
 
-    def denoised(self, **params) -> np.ndarray:
+    @property
+    def moments(self) -> np.ndarray:
+        """The running moments of the per-batch mean luminance (rtw_moments_update): (2, W * H, 4), allocated at
+        the first use, all zeros (the reset state) then and after the writer's scrub()."""
+        w = self.writer
+        if w.moments is None:
+            w.moments = np.zeros((2, w.width * w.height, 4), np.float32)
+        return w.moments
+
+    def update_moments(self):
+        """Fold what the accumulator gained since the last call into the moments; (err, tile_max, summary) of
+        World.noise_estimate are one call away."""
+        w = self.writer
+        return self.world.moments_update(w.buffer, self.moments, w.width, w.height)
+
+    def denoised(self, guided: bool = False, **params) -> np.ndarray:
         """The preview of what has been rendered so far: the world's guide buffers for this camera
         (World.render_guides) and the a-trous filter over the accumulator (World.denoise; params as there).
         Returns a new accumulator-form buffer -- update_texture-style consumers, the encoders and the
-        checkpoints take it as they take the accumulator -- and leaves the state's own accumulator alone."""
+        checkpoints take it as they take the accumulator -- and leaves the state's own accumulator alone.
+        guided=True: the variance-guided filter (World.denoise_guided) with the state's moments, brought up to
+        date first; pixels whose variance is still unknown are filtered by the guides alone."""
         cam = self.camera
         if cam.derived is None:
             cam.init()
         guides = self.world.render_guides(cam)
-        return self.world.denoise(self.writer.buffer, guides, cam.derived.image_width, cam.derived.image_height,
-                                  **params)
+        w, h = cam.derived.image_width, cam.derived.image_height
+        if guided:
+            return self.world.denoise_guided(self.writer.buffer, self.update_moments(), guides, w, h, **params)
+        return self.world.denoise(self.writer.buffer, guides, w, h, **params)
 
     def checkpoint(self, path: str, spp_done: int) -> None:
         """Write the accumulator + camera/seed/scene hash (rtw_checkpoint_write)."""
@@ -222,23 +244,32 @@ class RayTraceState:
 
 
 def progressive_render(state: RayTraceState, spp_begin: int = 0, batch: int = 1,
-                       on_batch: Optional[Callable[[int, float], bool]] = None) -> int:
+                       on_batch: Optional[Callable[[int, float], bool]] = None,
+                       until_noise: Optional[float] = None, noise_floor: float = 0.01) -> int:
     """Interactive-style render: samples [spp_begin, spp) in batches of `batch` over the
     whole image, refreshing the texture after each (what the UI shows) and calling
     on_batch(samples_done_per_pixel, count_samples()) -- return True to stop (the
     reference's Stop button, main.zig:58-60).  Consecutive batches are bit-identical to
-    one render.  Returns the samples per pixel done."""
+    one render.  Returns the samples per pixel done.
+    until_noise: a threshold on the per-pixel error sqrt(v) / (|mean| + noise_floor) of the mean luminance
+    (World.noise_estimate): the state's moments are updated after each batch and the render stops once no pixel
+    is over it -- not before two batches, a single one giving no variance.  None: no moments are touched."""
     cam = state.camera
     if cam.derived is None:
         cam.init()
     s = spp_begin
     spp = cam.samples_per_pixel
+    w, h = cam.derived.image_width, cam.derived.image_height
     while s < spp and state.running.value:
         e = min(spp, s + batch)
         cam.render_range(state, 0, cam.size, s, e)
         s = e
         if on_batch is not None and on_batch(s, state.count_samples()):
             break
+        if until_noise is not None:
+            summary = state.world.noise_estimate(state.update_moments(), w, h, until_noise, noise_floor)[2]
+            if summary.over == 0:
+                break
     return s
 
 

@@ -689,6 +689,8 @@ void rtw_scene_destroy(rtw_ctx* ctx) {
     if (ctx->d_env) (void)hipFree(ctx->d_env);
     for (float4* p : ctx->d_dn)
         if (p) (void)hipFree(p);
+    for (float* p : ctx->d_dnv)
+        if (p) (void)hipFree(p);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;

@@ -471,6 +471,10 @@ struct rtw_ctx {
     float4* d_dn[2] = {nullptr, nullptr};
     uint64_t dn_cap = 0;
     std::vector<float4> dn_host[2];
+    // the guided filter's two variance planes (one float per pixel) beside them, grown the same way
+    float* d_dnv[2] = {nullptr, nullptr};
+    uint64_t dnv_cap = 0;
+    std::vector<float> dnv_host[2];
 };
 // What the entry points of rtw_denoise.hip share with the render entry points (rtw_host.hip; the caller holds
 // ctx->mu): the launch of a camera on a context, and the stream ordering of consecutive calls on it

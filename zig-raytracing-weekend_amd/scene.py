@@ -912,6 +912,62 @@ class World:
                                           C.byref(p), out.ctypes.data), "rtw_denoise")
         return out
 
+    # ---- noise estimates and the guided filter (DESIGN.md §Noise estimates and the guided filter)
+    @staticmethod
+    def _frame(a, words: int, name: str, writable: bool = False) -> np.ndarray:
+        if not (isinstance(a, np.ndarray) and a.flags["C_CONTIGUOUS"] and a.dtype == np.float32 and a.size == words
+                and (a.flags["WRITEABLE"] or not writable)):
+            raise ValueError(f"{name} is not a contiguous float32 array of {words} words")
+        return a
+
+    def moments_update(self, accum: np.ndarray, moments: np.ndarray, width: int, height: int) -> np.ndarray:
+        """rtw_moments_update: fold what `accum` (W * H, 4) gained since the last update into `moments`
+        (2, W * H, 4) -- plane 0 the accumulator then, plane 1 (mean, M2, n, sw) of the per-batch mean luminance; all
+        zeros is the reset state -- in place.  Returns `moments`."""
+        n = int(width) * int(height)
+        self._frame(accum, 4 * n, "moments_update: accum")
+        self._frame(moments, 8 * n, "moments_update: moments", writable=True)
+        _abi.check(_abi.lib().rtw_moments_update(self.handle, width, height, accum.ctypes.data, moments.ctypes.data),
+                   "rtw_moments_update")
+        return moments
+
+    def noise_estimate(self, moments: np.ndarray, width: int, height: int, threshold: float = 0.05,
+                       floor: float = 0.01) -> tuple:
+        """rtw_noise_estimate: (err, tile_max, summary) -- err (W * H,) = sqrt(v) / (|mean| + floor), +inf where the
+        variance is unknown (fewer than two batches); tile_max (ceil(H / 8), ceil(W / 8)) its maximum over each
+        8 x 8 tile; summary an RtwNoiseSummary: over (pixels with err > threshold), known, max_err."""
+        n = int(width) * int(height)
+        self._frame(moments, 8 * n, "noise_estimate: moments")
+        err = np.empty(n, np.float32)
+        tiles = np.empty(((height + 7) // 8, (width + 7) // 8), np.float32)
+        s = _abi.RtwNoiseSummary()
+        _abi.check(_abi.lib().rtw_noise_estimate(self.handle, width, height, moments.ctypes.data, floor, threshold,
+                                                 err.ctypes.data, tiles.ctypes.data, C.byref(s)), "rtw_noise_estimate")
+        return err, tiles, s
+
+    def denoise_guided(self, accum: np.ndarray, moments: np.ndarray, guides, width: int, height: int,
+                       variance: bool = False, out: Optional[np.ndarray] = None, **params):
+        """rtw_denoise_guided: the variance-guided a-trous filter over `accum` with the moments of moments_update;
+        guides and `out` as denoise().  params: rtw_denoise_params fields over rtw_denoise_guided_defaults()
+        (sigma_color in standard deviations).  Returns the accumulator-form result, or with variance=True
+        (result, variance_out): the variance of the filtered mean luminance, -1 where unknown."""
+        albedo, nd = guides
+        p = _abi.denoise_guided_params(**params)
+        n = int(width) * int(height)
+        acc = self._frame(np.ascontiguousarray(accum, np.float32), 4 * n, "denoise_guided: accum")
+        nd = self._frame(np.ascontiguousarray(nd, np.float32), 4 * n, "denoise_guided: normal_depth")
+        if albedo is not None:
+            albedo = self._frame(np.ascontiguousarray(albedo, np.float32), 4 * n, "denoise_guided: albedo")
+        self._frame(moments, 8 * n, "denoise_guided: moments")
+        if out is None:
+            out = np.empty((n, 4), np.float32)
+        self._frame(out, 4 * n, "denoise_guided: out", writable=True)
+        var = np.empty(n, np.float32) if variance else None
+        _abi.check(_abi.lib().rtw_denoise_guided(self.handle, width, height, _abi.ptr(acc), moments.ctypes.data,
+                                                 _abi.ptr(albedo), _abi.ptr(nd), C.byref(p), out.ctypes.data,
+                                                 _abi.ptr(var)), "rtw_denoise_guided")
+        return (out, var) if variance else out
+
     # ---- ray queries (rtw_trace_rays / rtw_occluded; DESIGN.md §Ray queries)
     @staticmethod
     def _rays(origins, dirs, tmax, time) -> np.ndarray:
