@@ -720,9 +720,9 @@ int rtw_debug_environment(rtw_ctx* ctx, uint32_t n, const float* dirs, const flo
  * out may alias accum; albedo may be NULL without DEMODULATE.  The two intermediate images belong to the context
  * and grow on demand; the calls take the context lock as renders do.  RTW_E_INVALID with a message, out untouched:
  * passes outside 1 .. RTW_DENOISE_MAX_PASSES, a negative or non-finite sigma, unknown flag bits, width * height == 0
- * (or beyond 2^32 - 1), a null required pointer, rtw_denoise_device on a host context.  Out of scope: temporal
- * filtering, a sharded multi-GPU filter (filter device 0's gathered frame), a pixel sub-range.  (The variance-guided
- * filter is rtw_denoise_guided, in the block after this one.)
+ * (or beyond 2^32 - 1), a null required pointer, rtw_denoise_device on a host context.  Out of scope: a sharded
+ * multi-GPU filter (filter device 0's gathered frame), a pixel sub-range.  (The variance-guided filter is
+ * rtw_denoise_guided, in the block after this one; temporal filtering is rtw_temporal_accumulate, after that.)
  * ------------------------------------------------------------------------- */
 #define RTW_DENOISE_MAX_PASSES 8
 enum { RTW_DENOISE_DEMODULATE = 1u };
@@ -792,8 +792,8 @@ int rtw_debug_expneg(uint32_t n, const float* x, float* out);
  * out may alias accum.  Refusals are rtw_denoise's, plus a null moments; each leaves every output untouched.  The
  * device forms take device buffers of a GPU context (the summary too), are enqueued on `stream` (NULL: the
  * context's) and take flags RTW_RENDER_NO_SYNC; the host-buffer forms serve both kinds of context.  Out of scope:
- * non-uniform sample counts, per-channel variance, temporal accumulation, moments in checkpoints, a sharded
- * multi-GPU estimate or filter, a pixel sub-range.
+ * non-uniform sample counts, per-channel variance, moments in checkpoints, a sharded multi-GPU estimate or filter,
+ * a pixel sub-range.  (Temporal accumulation is rtw_temporal_accumulate, in the block after this one.)
  * ------------------------------------------------------------------------- */
 typedef struct rtw_noise_summary {       /* 24 bytes */
     uint64_t over, known;
@@ -817,6 +817,84 @@ int rtw_denoise_guided_device(rtw_ctx* ctx, uint32_t width, uint32_t height, con
                               const float* d_moments, const float* d_albedo, const float* d_normal_depth,
                               const rtw_denoise_params* params, float* d_out, float* d_variance_out, void* stream,
                               uint32_t flags);
+
+/* ---------------------------------------------------------------------------
+ * Temporal reprojection: SVGF's temporal half (Schied et al. 2017).  When the camera of a static scene moves, the
+ * accumulator and the moments of the previous camera are carried onto the new one instead of being scrubbed: the
+ * guide buffers place every pixel's first hit in world space (normal_depth.w is its distance from the camera
+ * centre), and the previous camera saw most of those points too.  The outputs keep the accumulator's and the
+ * moments' forms, so rtw_noise_estimate, rtw_denoise_guided, the encoders and further renders take them unchanged.
+ * A caller detects the capability by the presence of these symbols (the ABI version and every struct above are those
+ * of ABI 8).  A kernel of its own: no render and no filter result changes by a bit.  All in fp32, every operation
+ * rounded singly in the association written (nothing contracted), one function for the host and the device: they
+ * agree bit for bit.  DESIGN.md §Temporal reprojection.
+ *
+ * Per pixel (x, y) of the current frame, dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z, primes = the previous camera:
+ *   look     d = ((pixel00 + du (x + off)) + dv (y + off)) - c;  u = d / sqrt(dot(d, d)) per component
+ *            hit (cur_normal_depth.w > 0):  p = c + u depth;  e = p - c';  dist = sqrt(dot(e, e))
+ *            miss:  e = u, a point at infinity
+ *   project  n = cross(du', dv'),  a = pixel00' - c',  na = dot(n, a)  (once per call);  lambda = na / dot(n, e);
+ *            unless 0 < lambda < inf the point is behind the previous camera: no history
+ *            r = e lambda - a;  fx = dot(r, du') / dot(du', du') - off';  fy = dot(r, dv') / dot(dv', dv') - off'
+ *            (fx, fy) = (i, j) is the centre of the previous frame's pixel (i, j).  rtw_debug_reproject runs exactly
+ *            this on the host: e = points[i] - c', or e = dirs[i];  ok = 0 and xy = 0 where there is no history
+ *   snap     rx = floor(fx + 1/2), ry = floor(fy + 1/2);  if |fx - rx| <= S and |fy - ry| <= S, S =
+ *            RTW_TEMPORAL_SNAP, the one tap (rx, ry) with weight 1: a still camera copies, it does not diffuse
+ *   taps     otherwise x0 = floor(fx), tx = fx - x0 (y likewise) and the taps, in this order, (x0, y0) with weight
+ *            (1 - tx)(1 - ty), (x0 + 1, y0) with tx (1 - ty), (x0, y0 + 1) with (1 - tx) ty, (x0 + 1, y0 + 1) with tx ty
+ *   valid    a tap q counts if its weight is > 0, it is on the image, prev_accum[q] is finite with w > 0, its hit
+ *            state (depth > 0) is the centre's and, for hits, |depth_q - dist| <= depth_tolerance dist and
+ *            dot(n_cur, n_q) >= normal_cos
+ *   hidden   for a hit centre, if any tap on the image with weight > 0 saw a nearer surface (0 < depth_q and
+ *            dist - depth_q > depth_tolerance dist, whatever its accumulator holds) no tap is valid: the footprint
+ *            straddles an occluder's silhouette, and a point the previous camera could not see must not take the
+ *            history of its visible neighbours.  (A farther or differently oriented tap is only skipped.)
+ *   blend   ws = the sum of the valid weights;  g_q = weight_q / ws;  h_i = sum of g_q w_q;
+ *            mean = sum of g_q (rgb_q (1 / w_q));  h = min(h_i, max_history)  (0 without a valid tap)
+ *            out.rgb = mean h + cur.rgb,  out.w = h + cur.w;  with h = 0 out = cur bit for bit.  A current pixel that
+ *            is not finite or has w <= 0 contributes nothing: out = (mean h, h), 0 without history either
+ *            history_out (W*H floats, may be NULL) = h
+ *   moments  (given prev_moments and out_moments, two float4[W*H] planes each as rtw_moments_update's)  over the
+ *            valid taps with n_q >= 1:  g'_q = weight_q / (the sum of their weights);  m = sum of g'_q m_q of plane 1's
+ *            (mean, M2, n, sw), zeros without such a tap;  where the cap bites (h_i > max_history)
+ *            m.sw = m.sw (h / h_i) -- M2 and n stay: s2 = M2 / (n - 1) is a per-sample variance;  then
+ *            rtw_moments_update's West step with k = cur.w, inv = 1 / k, y = luma(cur.rgb inv), skipped for a current
+ *            pixel that contributes nothing or a y that is not finite.  out plane 1 = m, out plane 0 = out_accum
+ * out_accum may be cur_accum itself.  RTW_E_INVALID with a message, every output untouched: an output that overlaps
+ * a prev_* buffer (they are gathered from) or any other buffer, cameras of different image sizes, a zero-sized
+ * image, a null required pointer, exactly one of prev_moments / out_moments, max_history or depth_tolerance not > 0
+ * or not finite, normal_cos outside [-1, 1] or NaN, non-zero params->flags, unknown flag bits,
+ * rtw_temporal_accumulate_device on a host context.
+ * rtw_temporal_accumulate: host buffers; GPU contexts (staged through a device block of the call's own) and host
+ * contexts.  rtw_temporal_accumulate_device: device buffers of a GPU context, enqueued on `stream` (NULL: the
+ * context's); flags: RTW_RENDER_NO_SYNC.  Both take the context lock and order themselves on the stream as the
+ * filters do.  Out of scope: view-dependent lag on metal and glass (the first hit only, as the guides), defocus,
+ * moving spheres (points are taken as static), a sharded multi-GPU frame, history in checkpoints.
+ * ------------------------------------------------------------------------- */
+#define RTW_TEMPORAL_SNAP 0.015625f      /* 2^-6 pixel: DESIGN.md §Temporal reprojection has the measured round-off */
+typedef struct rtw_temporal_params {     /* 32 bytes */
+    float max_history;                   /* cap on the history's weight in samples; > 0 */
+    float depth_tolerance;               /* relative: |d_prev_tap - |p - c_prev|| <= tol * |p - c_prev|; > 0 */
+    float normal_cos;                    /* a tap is valid if dot(n_cur, n_prev_tap) >= normal_cos; in [-1, 1] */
+    uint32_t flags;                      /* none yet: non-zero refused */
+    float _pad[4];
+} rtw_temporal_params;
+/* The shipped parameters: the winner of the grid search recorded in profiles/temporal/defaults.json. */
+void rtw_temporal_defaults(rtw_temporal_params* p);
+int rtw_temporal_accumulate(rtw_ctx* ctx, const rtw_camera* cur_cam, const rtw_camera* prev_cam,
+                            const float* cur_accum, const float* cur_normal_depth, const float* prev_accum,
+                            const float* prev_normal_depth, const float* prev_moments,
+                            const rtw_temporal_params* params, float* out_accum, float* out_moments,
+                            float* history_out);
+int rtw_temporal_accumulate_device(rtw_ctx* ctx, const rtw_camera* cur_cam, const rtw_camera* prev_cam,
+                                   const float* d_cur_accum, const float* d_cur_normal_depth,
+                                   const float* d_prev_accum, const float* d_prev_normal_depth,
+                                   const float* d_prev_moments, const rtw_temporal_params* params, float* d_out_accum,
+                                   float* d_out_moments, float* d_history_out, void* stream, uint32_t flags);
+/* Host-only (no context): the projection step above for n points (points[3 i ..], dirs NULL) or n directions
+ * (dirs[3 i ..], points NULL): xy[2 i ..] = (fx, fy), ok[i] = 1, or ok[i] = 0 behind the camera. */
+int rtw_debug_reproject(const rtw_camera* prev_cam, uint32_t n, const float* points, const float* dirs, float* xy,
+                        uint8_t* ok);
 
 /* ---------------------------------------------------------------------------
  * Ray queries: the closest hit, or whether anything is hit, for rays the caller supplies -- picking (the object

@@ -217,6 +217,26 @@ class RtwNoiseSummary(C.Structure):
     _fields_ = [("over", C.c_uint64), ("known", C.c_uint64), ("max_err", C.c_float), ("_pad", C.c_uint32)]
 
 
+RTW_TEMPORAL_SNAP = 2.0 ** -6  # pixels: a reprojection this close to a pixel centre takes that one tap
+
+
+class RtwTemporalParams(C.Structure):
+    # rtw_temporal_params (32 bytes): the history's cap in samples and the two tap tests of the reprojection
+    _fields_ = [("max_history", C.c_float), ("depth_tolerance", C.c_float), ("normal_cos", C.c_float),
+                ("flags", C.c_uint32), ("_pad", C.c_float * 4)]
+
+
+def temporal_params(**fields) -> RtwTemporalParams:
+    """rtw_temporal_defaults() with `fields` overridden."""
+    p = RtwTemporalParams()
+    lib().rtw_temporal_defaults(C.byref(p))
+    for k, v in fields.items():
+        if k.startswith("_") or not hasattr(p, k):
+            raise KeyError(f"rtw_temporal_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
 class RtwEnvironment(C.Structure):
     # rtw_environment (40 bytes): an equirectangular radiance map, row 0 = +y
     _fields_ = [("rgb", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("scale", F3),
@@ -356,6 +376,15 @@ SIGNATURES = {
     "rtw_denoise_guided_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.POINTER(RtwDenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint32]),
+    "rtw_temporal_defaults": (None, [C.POINTER(RtwTemporalParams)]),
+    "rtw_temporal_accumulate": (C.c_int, [C.c_void_p, C.POINTER(RtwCamera), C.POINTER(RtwCamera), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtwTemporalParams), C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "rtw_temporal_accumulate_device": (C.c_int, [C.c_void_p, C.POINTER(RtwCamera), C.POINTER(RtwCamera), C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(RtwTemporalParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_uint32]),
+    "rtw_debug_reproject": (C.c_int, [C.POINTER(RtwCamera), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtw_trace_rays": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "rtw_trace_rays_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "rtw_occluded": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -215,6 +215,37 @@ class RayTraceState:
             return self.world.denoise_guided(self.writer.buffer, self.update_moments(), guides, w, h, **params)
         return self.world.denoise(self.writer.buffer, guides, w, h, **params)
 
+    def move_camera(self, camera: Camera, spp: int, **params) -> np.ndarray:
+        """Change the camera without scrubbing (the reference's sliders scrub, src/main.zig:523-546): render `spp`
+        samples of `camera` into a fresh frame, reproject the state's accumulator and moments -- those of the camera
+        so far -- onto it (World.temporal_accumulate; params as there) and install the result, the new camera and its
+        guides, which serve as the next call's "previous".  The image size must stay.  Every call draws fresh
+        samples: call k renders with seed + k.  Returns the history (W * H,): the weight in samples each pixel took
+        over, 0 where the new camera sees what the old one did not."""
+        w = self.writer
+        prev = self.camera
+        for c in (prev, camera):
+            if c.derived is None:
+                c.init()
+        if (camera.derived.image_width, camera.derived.image_height) != (w.width, w.height):
+            raise ValueError("move_camera: the new camera's image size differs from the writer's")
+        kept = getattr(self, "_guides", None)
+        prev_nd = kept[1][1] if kept is not None and kept[0] == bytes(prev.derived) else self.world.render_guides(prev)[1]
+        self._moves = getattr(self, "_moves", 0) + 1
+        cur = np.zeros((camera.size, 4), np.float32)
+        _abi.check(_abi.lib().rtw_render(self.world.handle, C.byref(camera.derived), 0, camera.size, 0, int(spp),
+                                         self.seed + self._moves, cur.ctypes.data, None, _abi.PROGRESS_FN(0), None),
+                   "rtw_render")
+        guides = self.world.render_guides(camera)
+        out, mom, hist = self.world.temporal_accumulate(camera, prev, cur, guides[1], w.buffer, prev_nd,
+                                                        self.update_moments(), **params)
+        w.buffer[...] = out
+        w.moments[...] = mom
+        w.update_texture()
+        self.camera = camera
+        self._guides = (bytes(camera.derived), guides)
+        return hist
+
     def checkpoint(self, path: str, spp_done: int) -> None:
         """Write the accumulator + camera/seed/scene hash (rtw_checkpoint_write)."""
         h = C.c_uint64()

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "rtw_device.h"
+#include "rtw_moments.h"
 
 namespace {
 
@@ -102,10 +103,6 @@ struct DnPass {
     uint32_t last, demod;
 };
 
-RTW_DHD bool dn_finite3(float4 c) {
-    return (fbits(c.x) & 0x7F800000u) != 0x7F800000u && (fbits(c.y) & 0x7F800000u) != 0x7F800000u &&
-           (fbits(c.z) & 0x7F800000u) != 0x7F800000u;
-}
 RTW_DHD float dn_floor(float a) { return a > 0x1p-8f ? a : 0x1p-8f; }  // max(albedo, 2^-8); a NaN: 2^-8
 
 RTW_DHD float4 dn_prepass(float4 a, const float4* albedo, size_t p) {
@@ -343,20 +340,16 @@ void host_filter(rtw_ctx* ctx, uint32_t W, uint32_t H, const float4* accum, cons
 // and the guided filter).  moments = two float4[W H] planes: the accumulator as of the last update, then
 // (mean, M2, n, sw).  Every function below is one rounded fp32 operation per step in the association written.
 // ---------------------------------------------------------------------------
-RTW_DHD float dn_luma(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-RTW_DHD bool dn_finite1(float v) { return (fbits(v) & 0x7F800000u) != 0x7F800000u; }
-
+// (dn_luma, dn_finite1 / dn_finite3 and West's update itself, mo_batch_luma and mo_west, are rtw_moments.h's: the
+// temporal reprojection of rtw_temporal.hip runs them too)
 // West's weighted update of one pixel by the batch a - p; false: neither plane changes
 RTW_DHD bool mo_update(float4 a, float4& p, float4& m) {
     const float k = a.w - p.w;
     if (!(k > 0.0f)) return false;
-    const float inv = 1.0f / k;
-    const float y = dn_luma((a.x - p.x) * inv, (a.y - p.y) * inv, (a.z - p.z) * inv);
+    const float y = mo_batch_luma(a.x - p.x, a.y - p.y, a.z - p.z, k);
     p = a;
     if (!dn_finite1(y)) return true;
-    const float sw = m.w + k, e = y - m.x;
-    const float mean = m.x + e * (k / sw);
-    m = make_float4(mean, m.y + (k * e) * (y - mean), m.z + 1.0f, sw);
+    mo_west(m, y, k);
     return true;
 }
 // The variance of the pixel's mean luminance, v = (M2 / (n - 1)) / sw; -1: unknown (n < 2).  What is not > 0 (a

@@ -968,6 +968,85 @@ class World:
                                                  _abi.ptr(var)), "rtw_denoise_guided")
         return (out, var) if variance else out
 
+    # ---- temporal reprojection (rtw_temporal_accumulate; DESIGN.md §Temporal reprojection)
+    @staticmethod
+    def _derived(cam) -> "_abi.RtwCamera":
+        if isinstance(cam, _abi.RtwCamera):
+            return cam
+        if cam.derived is None:
+            cam.init()
+        return cam.derived
+
+    def temporal_accumulate(self, cur_cam, prev_cam, cur_accum: np.ndarray, cur_normal_depth: np.ndarray,
+                            prev_accum: np.ndarray, prev_normal_depth: np.ndarray,
+                            prev_moments: Optional[np.ndarray] = None, out: Optional[np.ndarray] = None,
+                            **params) -> tuple:
+        """rtw_temporal_accumulate: carry the previous camera's accumulator (and moments) onto the current camera's
+        frame and add the current frame's samples.  cur_* / prev_*: float32 (W * H, 4) accumulators and the
+        normal_depth guides of render_guides for the two cameras (Camera or RtwCamera); prev_moments: (2, W * H, 4)
+        or None.  params: rtw_temporal_params fields over rtw_temporal_defaults().  Returns (accum, moments | None,
+        history): history (W * H,) is the weight in samples each pixel took over.  out: where to put accum; it may be
+        cur_accum itself."""
+        cc, pc = self._derived(cur_cam), self._derived(prev_cam)
+        n = int(cc.size)
+        p = _abi.temporal_params(**params)
+        for a, name in ((cur_accum, "cur_accum"), (cur_normal_depth, "cur_normal_depth"), (prev_accum, "prev_accum"),
+                        (prev_normal_depth, "prev_normal_depth")):
+            self._frame(a, 4 * n, f"temporal_accumulate: {name}")
+        mom = None
+        if prev_moments is not None:
+            self._frame(prev_moments, 8 * n, "temporal_accumulate: prev_moments")
+            mom = np.empty((2, n, 4), np.float32)
+        if out is None:
+            out = np.empty((n, 4), np.float32)
+        self._frame(out, 4 * n, "temporal_accumulate: out", writable=True)
+        hist = np.empty(n, np.float32)
+        _abi.check(_abi.lib().rtw_temporal_accumulate(
+            self.handle, C.byref(cc), C.byref(pc), cur_accum.ctypes.data, cur_normal_depth.ctypes.data,
+            prev_accum.ctypes.data, prev_normal_depth.ctypes.data, _abi.ptr(prev_moments), C.byref(p), out.ctypes.data,
+            _abi.ptr(mom), hist.ctypes.data), "rtw_temporal_accumulate")
+        return out, mom, hist
+
+    def temporal_accumulate_device(self, cur_cam, prev_cam, cur_accum, cur_normal_depth, prev_accum,
+                                   prev_normal_depth, prev_moments=None, out=None, stream=None, **params) -> tuple:
+        """rtw_temporal_accumulate_device on torch CUDA tensors, shaped as temporal_accumulate's arrays.  Returns
+        (accum, moments | None, history) tensors.  stream=None: on torch's current stream, finished on return; a
+        torch.cuda.Stream: enqueued there, not synchronised."""
+        import torch
+        cc, pc = self._derived(cur_cam), self._derived(prev_cam)
+        n = int(cc.size)
+        p = _abi.temporal_params(**params)
+
+        def frame(t, words, name):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                    and t.numel() == words and t.device.index == self.device):
+                raise ValueError(f"temporal_accumulate_device: {name} is not a contiguous float32 tensor of {words} "
+                                 f"words on device {self.device}")
+            return t
+        for t, name in ((cur_accum, "cur_accum"), (cur_normal_depth, "cur_normal_depth"), (prev_accum, "prev_accum"),
+                        (prev_normal_depth, "prev_normal_depth")):
+            frame(t, 4 * n, name)
+        dev = cur_accum.device
+        mom = None
+        if prev_moments is not None:
+            frame(prev_moments, 8 * n, "prev_moments")
+            mom = torch.empty((2, n, 4), dtype=torch.float32, device=dev)
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        frame(out, 4 * n, "out")
+        hist = torch.empty(n, dtype=torch.float32, device=dev)
+        if stream is None:
+            handle, flags = torch.cuda.current_stream(dev).cuda_stream, 0
+        else:
+            handle, flags = stream.cuda_stream, _abi.RTW_RENDER_NO_SYNC
+        _abi.check(_abi.lib().rtw_temporal_accumulate_device(
+            self.handle, C.byref(cc), C.byref(pc), cur_accum.data_ptr(), cur_normal_depth.data_ptr(),
+            prev_accum.data_ptr(), prev_normal_depth.data_ptr(),
+            prev_moments.data_ptr() if prev_moments is not None else None, C.byref(p), out.data_ptr(),
+            mom.data_ptr() if mom is not None else None, hist.data_ptr(), C.c_void_p(handle), flags),
+            "rtw_temporal_accumulate_device")
+        return out, mom, hist
+
     # ---- ray queries (rtw_trace_rays / rtw_occluded; DESIGN.md §Ray queries)
     @staticmethod
     def _rays(origins, dirs, tmax, time) -> np.ndarray:
