@@ -362,7 +362,10 @@ typedef struct rtw_tuning {
     uint64_t wf_paths;         /* wavefront batch capacity in paths; 0 = auto (2^29 within 35 % of free memory) */
     uint32_t tile_lists;       /* camera rays of static sphere scenes (fused step) test per-8x8-tile candidate lists:
                                   0 = off, 1 = default (lists of <= 32 spheres, 128 for trees of > 4096 nodes),
-                                  2..128 = that cap (ABI 4; 128 since ABI 8) */
+                                  2..128 = that cap (ABI 4; 128 since ABI 8).  A tile with more candidates than the
+                                  cap walks the tree.  Trees of <= 4096 nodes build the lists by a flat scan of the
+                                  leaves, larger ones by a frustum walk of the tree; both serve every cap
+                                  (rtw_debug_tile_lists reads them back) */
     uint32_t hoist;            /* SAH sphere scenes: spheres whose box dwarfs the rest of the scene (a ground
                                   sphere) are tested first by every walk, ahead of the tree (default 1; ABI 5) */
     uint32_t sort_iters;       /* fused step (trees staged in LDS): wavefront iterations 0 .. sort_iters-1 file
@@ -1019,6 +1022,31 @@ int rtw_debug_quad_shade(uint32_t n, const rtw_quad* quads, const rtw_vertex_att
  * counters (slots used per output stripe, of the last iterations' queues; a set already reset reads 0).  No
  * counter may exceed the capacity: the queues are not bound-checked on the device. */
 int rtw_debug_stripe_counters(rtw_ctx* ctx, uint32_t* stripe_cap, uint32_t counters[768]);
+/* GPU contexts (detected by the symbol's presence; the ABI version and every struct are those of ABI 8): the
+ * camera-ray candidate lists (rtw_tuning.tile_lists) that a render of pixels [pix_begin, pix_end) with this camera
+ * would build, read back.  The launch and its 8x8 tiles are set up as rtw_render_device sets them up; the context's
+ * list buffer is filled with 0xFF, one builder runs -- builder 0: the one a render picks, 1: the flat scan, 2: the
+ * frustum walk; both run on any tree with compact nodes -- and nothing else: no render kernel, no accumulator.
+ * cap 0 = the context's cap, 2..128 = that cap for this call.  *n_tiles tiles, tile t covering x in
+ * 8 (t % *n_tx) .. +7 and rows *row0 + 8 (t / *n_tx) .. +7, clipped to the image and the pixel range; counts[t] =
+ * the tile's candidates, 0xFFFFFFFF when they exceed the cap (the tile walks the tree); entries[8 (t cap + k) ..] =
+ * entry k as the device holds it: bits(centre.xyz), bits(radius * radius), the ordering-0 leaf index, bits(tlow: a
+ * lower bound of the ray parameter of a hit), 0, 0, sorted by (tlow, index).  A slot no builder wrote has index
+ * 0xFFFFFFFF.  RTW_E_INVALID: a host context, a context that renders without lists (objects, media, moving
+ * spheres, fewer than 4 orderings, no compact nodes, tile_lists 0, a camera of max_depth 0), an empty range, or
+ * tiles_cap < *n_tiles (which is set first: counts holds tiles_cap words, entries 8 * cap * tiles_cap). */
+int rtw_debug_tile_lists(rtw_ctx* ctx, const rtw_camera* cam, uint32_t pix_begin, uint32_t pix_end, uint32_t builder,
+                         uint32_t cap, uint32_t* n_tiles, uint32_t* n_tx, uint32_t* row0, uint32_t* counts,
+                         uint32_t* entries, uint32_t tiles_cap);
+/* Host-only (no context): tile_frustum and tile_reach -- the geometry of both list builders, the same fp32
+ * operations -- for the tile whose rendered pixels span [x0, x1] x [y0, y1] (the camera's pixel_offset applied as a
+ * render applies it) and n spheres centres[3 i ..], radii[i]: reach[i] = 1 if a camera ray of the tile may hit the
+ * sphere (conservative), tlow[i] = the lower bound of such a hit's ray parameter (0 when the sphere reaches the
+ * camera plane or is rejected behind it).  *frame_ok (may be NULL) = 0 when the camera's pixel plane gives no frame
+ * (pixel_delta_u, pixel_delta_v not orthogonal to 1e-4, or the plane not in front of the centre): the builders then
+ * send every tile to the tree walk. */
+int rtw_debug_tile_reach(const rtw_camera* cam, float x0, float x1, float y0, float y1, uint32_t n,
+                         const float* centres, const float* radii, uint8_t* reach, float* tlow, uint8_t* frame_ok);
 
 #ifdef __cplusplus
 }

@@ -333,6 +333,7 @@ def test_v1_knobs_invariant(rtw, book1, knob):
 @pytest.mark.parametrize("knob", [{"wf_iters": 1}, {"wf_iters": 9}, {"wf_iters": 50}, {"wf_paths": 4096}, {"fast_box": 0},
                                   {"lds": 127 & ~1}, {"sah_max_leaf": 4}, {"compact_nodes": 0}, {"lds": 127 & ~2},
                                   {"fuse": 0}, {"fuse": 1}, {"lds": 127 & ~4}, {"bvh_orders": 1}, {"tile_lists": 0}, {"tile_lists": 2}, {"tile_lists": 64},
+                                  {"tile_lists": 128}, {"tile_lists": 65},
                                   {"lds": 127 & ~2, "wide_walk": 0}, {"fuse": 5}, {"lds": 127 & ~2, "fuse": 5},
                                   {"lds": 127 & ~2, "fuse": 5, "wide_walk": 0}, {"hoist": 0}, {"hoist": 0, "fuse": 0},
                                   {"sort_iters": 0}, {"sort_iters": 50}, {"sort_iters_split": 50, "fuse": 0}, {"sort_iters_split": 0, "fuse": 0},
@@ -544,7 +545,8 @@ def test_tile_lists_random_cameras(rtw, book1, cam_seed):
     spheres a tile's jittered, defocused rays can reach) never change a pixel, for
     random cameras: inside and around the sphere field, wide and narrow fields of
     view, strong defocus, near focus planes, the +1 pixel quirk -- bit-identical to
-    the walk."""
+    the walk, at the default cap and at the largest (128: lists longer than the 64 lanes
+    of the block that builds them)."""
     arr, _ = book1
     g = np.random.default_rng(100 + cam_seed)
     lookfrom = tuple(float(v) for v in g.uniform([-14, 0.3, -14], [14, 6, 14]))
@@ -555,9 +557,10 @@ def test_tile_lists_random_cameras(rtw, book1, cam_seed):
                      defocus_angle=float(g.choice([0.0, 0.6, 4.0, 12.0])),
                      focus_dist=float(g.uniform(0.5, 20))).init()
     outs = []
-    for tl in (0, 1):
+    for tl in (0, 1, 128):
         w = rtw.World(arr, tuning={"tile_lists": tl})
         outs.append(render_rows(rtw, w, cam, 0, cam.derived.image_height, 0, 3, cam_seed))
         w.close()
     assert np.isfinite(outs[1]).all()
     assert np.array_equal(outs[0], outs[1])
+    assert np.array_equal(outs[0], outs[2])

@@ -354,6 +354,11 @@ SIGNATURES = {
     "rtw_debug_quad_shade": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "rtw_debug_stripe_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
+    "rtw_debug_tile_lists": (C.c_int, [C.c_void_p, C.POINTER(RtwCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p,
+                                       C.c_void_p, C.c_uint32]),
+    "rtw_debug_tile_reach": (C.c_int, [C.POINTER(RtwCamera), C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtw_denoise_defaults": (None, [C.POINTER(RtwDenoiseParams)]),
     "rtw_render_guides": (C.c_int, [C.c_void_p, C.POINTER(RtwCamera), C.c_void_p, C.c_void_p]),
     "rtw_render_guides_device": (C.c_int, [C.c_void_p, C.POINTER(RtwCamera), C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1225,12 +1225,31 @@ size_t wf_state_bytes(uint64_t Q, uint64_t P) {
 static_assert(RTW_WF_PATH_BYTES == 2 * (4 * 16 + 8) + 8 + sizeof(rtw_rgb),
               "RTW_WF_PATH_BYTES = wf_state_bytes per path");
 
+// The launch's 8x8 tiles over its rows (W.n_tx; returns the logical pixels, 64 per tile) and the context's
+// camera-ray candidate lists for them (the compact-LDS fused step of static sphere scenes, rtw_tuning.tile_lists):
+// W.tl / W.tl_count, left null when the launch has none.  (run_wavefront and rtw_debug_tile_lists)
+uint64_t wf_tile_grid(const rtw_launch& L, rtw_wf& W) {
+    W.n_tx = (L.W + 7) / 8;
+    return (uint64_t)W.n_tx * ((L.n_rows + 7) / 8) * 64;
+}
+void wf_tile_buffer(rtw_ctx* ctx, const rtw_launch& L, rtw_wf& W, uint64_t n_pix, hipStream_t stream) {
+    if (L.tile_lists && L.cnodes && L.n_orders >= 4) {
+        const uint64_t tiles = n_pix / 64;
+        if (ctx->tl_cap < tiles &&
+            rtw_device_grow(&ctx->d_tl, &ctx->tl_cap, tiles, tiles * RTW_TL_BYTES + 256, stream) != hipSuccess)
+            (void)hipGetLastError();  // no lists: the walk
+        if (ctx->tl_cap >= tiles) {
+            W.tl = static_cast<uint4*>(ctx->d_tl);
+            W.tl_count = reinterpret_cast<uint32_t*>(static_cast<char*>(ctx->d_tl) + tiles * RTW_TL_MAX * 32);
+        }
+    }
+}
+
 // Wavefront (v2) render of samples [L.s0, L.s1): batches of n_s samples so that
 // n_pix * n_s paths fit the path-state buffer (grown on demand, kept in the ctx).
 int run_wavefront(rtw_ctx* ctx, rtw_launch L, hipStream_t stream, rtw_timer* T) {
     rtw_wf W{};
-    W.n_tx = (L.W + 7) / 8;
-    const uint64_t n_pix = (uint64_t)W.n_tx * ((L.n_rows + 7) / 8) * 64;
+    const uint64_t n_pix = wf_tile_grid(L, W);
     const uint32_t spp = L.s1 - L.s0;
     uint64_t n_s = std::max<uint64_t>(1, ctx->wf_max_paths / n_pix);
     if (n_s > spp) n_s = spp;
@@ -1294,17 +1313,7 @@ int run_wavefront(rtw_ctx* ctx, rtw_launch L, hipStream_t stream, rtw_timer* T) 
     W.sort_iters_split = ctx->wf_sort_iters_split;
     W.sort_mask = ctx->wf_sort_mask;
     W.run_log2 = 4;  // set per launch grid by wf_coherence (rtw_wavefront.hip)
-    // camera-ray candidate lists (the compact-LDS fused step of static sphere scenes, rtw_tuning.tile_lists)
-    if (L.tile_lists && L.cnodes && L.n_orders >= 4) {
-        const uint64_t tiles = n_pix / 64;
-        if (ctx->tl_cap < tiles &&
-            rtw_device_grow(&ctx->d_tl, &ctx->tl_cap, tiles, tiles * RTW_TL_BYTES + 256, stream) != hipSuccess)
-            (void)hipGetLastError();  // no lists: the walk
-        if (ctx->tl_cap >= tiles) {
-            W.tl = static_cast<uint4*>(ctx->d_tl);
-            W.tl_count = reinterpret_cast<uint32_t*>(static_cast<char*>(ctx->d_tl) + tiles * RTW_TL_MAX * 32);
-        }
-    }
+    wf_tile_buffer(ctx, L, W, n_pix, stream);
     const uint32_t s_end = L.s1;
     for (uint32_t s = L.s0; s < s_end; s += (uint32_t)n_s) {
         L.s0 = s;
@@ -1745,6 +1754,46 @@ int rtw_debug_stripe_counters(rtw_ctx* ctx, uint32_t* stripe_cap, uint32_t* coun
     HIP_TRY(hipMemcpy(raw.data(), ctx->wf_len, raw.size() * 4, hipMemcpyDeviceToHost));
     for (uint32_t k = 0; k < 3u * RTW_WF_STRIPES; k++) counters[k] = raw[(size_t)k * RTW_WF_LEN_STRIDE];
     *stripe_cap = ctx->wf_stripe_cap;
+    return RTW_OK;
+}
+
+int rtw_debug_tile_lists(rtw_ctx* ctx, const rtw_camera* cam, uint32_t pix_begin, uint32_t pix_end, uint32_t builder,
+                         uint32_t cap, uint32_t* n_tiles, uint32_t* n_tx, uint32_t* row0, uint32_t* counts,
+                         uint32_t* entries, uint32_t tiles_cap) {
+    if (!ctx || !n_tiles || !n_tx || !row0) return fail(RTW_E_INVALID, "null args");
+    if (ctx->device == RTW_DEVICE_CPU) return fail(RTW_E_INVALID, "host context");
+    if (int rc = rtw_validate_cam(cam)) return rc;
+    if (pix_end > cam->size || pix_begin >= pix_end) return fail(RTW_E_INVALID, "pixel range empty or out of image");
+    if (builder > 2 || (cap && (cap < 2 || cap > RTW_TL_MAX)))
+        return fail(RTW_E_INVALID, "rtw_debug_tile_lists: builder is 0..2, cap 0 or 2..128");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    if (int rc = stream_enter(ctx, s)) return rc;
+    ctx->last_stream = nullptr;  // synchronised below
+    // the launch and the batch's tiles as rtw_render_device makes them
+    rtw_launch L = make_launch(ctx, cam, 0);
+    set_plain_range(L, pix_begin, pix_end);
+    rtw_wf W{};
+    const uint64_t n_pix = wf_tile_grid(L, W);
+    const uint64_t tiles = n_pix / 64;
+    W.n_pix = (uint32_t)n_pix;
+    *n_tiles = (uint32_t)tiles;
+    *n_tx = W.n_tx;
+    *row0 = L.row0;
+    wf_tile_buffer(ctx, L, W, n_pix, s);
+    if (!W.tl_count) return fail(RTW_E_INVALID, "rtw_debug_tile_lists: the context renders without tile lists");
+    if (tiles > tiles_cap || !counts || !entries) return fail(RTW_E_INVALID, "rtw_debug_tile_lists: tiles_cap too small");
+    if (cap) L.tile_lists = cap;
+    // a slot no builder wrote reads back as id 0xFFFFFFFF
+    HIP_TRY(hipMemsetAsync(ctx->d_tl, 0xFF, tiles * RTW_TL_BYTES, s));
+    if (!rtw_wavefront_tile_lists(L, W, s, builder))
+        return fail(RTW_E_INVALID, "rtw_debug_tile_lists: the scene class renders without tile lists");
+    HIP_TRY(hipGetLastError());
+    const size_t row = (size_t)L.tile_lists * 32;
+    HIP_TRY(hipMemcpyAsync(counts, W.tl_count, tiles * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpy2DAsync(entries, row, W.tl, (size_t)RTW_TL_MAX * 32, row, tiles, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return RTW_OK;
 }
 

@@ -102,3 +102,7 @@ struct rtw_wf {
 void rtw_wavefront_batch(const rtw_launch& L, const rtw_wf& W, void* stream, int n_cu, rtw_timer* T);
 // waves of the largest wavefront grid (bounds the stripe capacity)
 uint32_t rtw_wavefront_max_waves(int n_cu);
+// rtw_debug_tile_lists: the camera-ray candidate lists of the batch alone (W: n_pix, n_tx, tl, tl_count), built by the
+// kernels of the launch's scene class -- builder 0: the one a render picks, 1: the flat scan, 2: the frustum walk.
+// false: the class renders without lists (nothing launched)
+bool rtw_wavefront_tile_lists(const rtw_launch& L, const rtw_wf& W, void* stream, uint32_t builder);

@@ -774,14 +774,15 @@ __device__ __forceinline__ int wf_traverse_global(const rtw_launch& L, const Ray
 // t >= (z - rho) / h.  Spheres wholly behind the camera plane (z < -rho) are never kept (a ray's
 // depth is t * h > 0); those straddling it are kept when near the axis (tile_reach).
 // The tile's ray set (see above): pixel rectangle at depth h in the (uh, vh) frame around the
-// camera centre, defocus radius rd, sec of the widest ray angle
+// camera centre, defocus radius rd, sec of the widest ray angle.  (tile_frustum and tile_reach are host + device:
+// rtw_debug_tile_reach runs the builders' fp32 geometry on the host.)
 struct TileFrustum {
     f3 ctr, fz, uh, vh;
     float h, ru0, ru1, rv0, rv1, rd, sec;
     bool ok;  // false: no usable frame (the tile walks the tree)
 };
 
-__device__ __forceinline__ TileFrustum tile_frustum(const rtw_launch& L, float x0, float x1, float y0, float y1) {
+RTW_DHD TileFrustum tile_frustum(const rtw_launch& L, float x0, float x1, float y0, float y1) {
     TileFrustum F;
     const f3 du = ld3(L.du), dv = ld3(L.dv);
     F.ctr = ld3(L.center);
@@ -812,7 +813,7 @@ __device__ __forceinline__ TileFrustum tile_frustum(const rtw_launch& L, float x
 
 // Can a ray of the tile pass within rho of c?  (conservative; tlow: a lower bound of the ray
 // parameter of any such hit, 0 when the sphere reaches the camera plane)
-__device__ __forceinline__ bool tile_reach(const TileFrustum& F, f3 c, float rho, float& tlow) {
+RTW_DHD bool tile_reach(const TileFrustum& F, f3 c, float rho, float& tlow) {
     const f3 cc = c - F.ctr;
     const float z = dot(cc, F.fz), cu = dot(cc, F.uh), cv = dot(cc, F.vh);
     const float slack = 1e-3f * (__builtin_fabsf(z) + __builtin_fabsf(cu) + __builtin_fabsf(cv) + rho) + 1e-5f;
@@ -907,7 +908,7 @@ __global__ __launch_bounds__(64) void wf_tile_lists(rtw_launch L, rtw_wf W) {
         return;
     }
     __syncthreads();
-    tile_emit(L, W, tile, s_t, s_id, count, lane);
+    for (uint32_t k = lane; k < count; k += 64u) tile_emit(L, W, tile, s_t, s_id, count, k);  // (count may exceed 64)
     if (lane == 0) W.tl_count[tile] = count;
 }
 

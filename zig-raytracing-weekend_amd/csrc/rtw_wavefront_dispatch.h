@@ -89,18 +89,34 @@ size_t wf_w2_lds(const rtw_launch& L) {
 }
 
 // The camera-ray candidate lists of a batch (static sphere scenes with the compact nodes): the
-// flat scan for small trees, the frustum walk for large ones.  Returns W with tl_count null when off.
+// flat scan for small trees, the frustum walk for large ones.  wf_lists returns W with tl_count null when off.
+template <uint32_t FEAT>
+bool wf_lists_on(const rtw_launch& L, const rtw_wf& W) {
+    return W.tl_count && L.cnodes && !(FEAT & (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_MOVING)) && L.max_depth != 0;
+}
+// one builder over the batch's tiles: the flat scan (one block per tile) or the frustum walk (one lane per tile)
+void wf_build_lists(const rtw_launch& L, const rtw_wf& W, hipStream_t st, bool scan) {
+    const uint32_t tiles = W.n_pix / 64u;
+    if (scan) wf_launch(wf_tile_lists, tiles, 64, 0, st, L, W);
+    else wf_launch(wf_tile_lists_walk, (tiles + 63u) / 64u, 64, 0, st, L, W);
+}
 template <uint32_t FEAT>
 rtw_wf wf_lists(const rtw_launch& L, const rtw_wf& W, hipStream_t st) {
     rtw_wf Wt = W;
-    if (!W.tl_count || !L.cnodes || (FEAT & (RTW_F_GEOM | RTW_F_MEDIUM | RTW_F_MOVING)) || L.max_depth == 0) {
+    if (!wf_lists_on<FEAT>(L, W)) {
         Wt.tl_count = nullptr;
         return Wt;
     }
-    const uint32_t tiles = W.n_pix / 64u;
-    if (L.n_nodes <= 4096u) wf_launch(wf_tile_lists, tiles, 64, 0, st, L, Wt);
-    else wf_launch(wf_tile_lists_walk, (tiles + 63u) / 64u, 64, 0, st, L, Wt);
+    wf_build_lists(L, Wt, st, L.n_nodes <= 4096u);
     return Wt;
+}
+// rtw_debug_tile_lists: the lists of class FEAT's batch alone, by wf_lists' builder (0), the scan (1) or the walk (2);
+// 0: the class renders without lists, 1: launched
+template <uint32_t FEAT>
+int wf_lists_only(const rtw_launch& L, const rtw_wf& W, hipStream_t st, uint32_t builder) {
+    if (!wf_lists_on<FEAT>(L, W)) return 0;
+    wf_build_lists(L, W, st, builder ? builder == 1u : L.n_nodes <= 4096u);
+    return 1;
 }
 
 // Coherent-queue settings of a launch whose grid has nw waves.  Iteration 0 deals runs of
@@ -414,6 +430,12 @@ struct WfClasses {
         return ((feat == F && (wf_run<F>(L, W, st, n_cu, T), true)) || ...);
     }
     static uint32_t max_waves(int n_cu) { return std::max({wf_class_waves<F>(n_cu)...}); }
+    // wf_lists_only of `feat` if it is one of them, else -1
+    static int lists(uint32_t feat, const rtw_launch& L, const rtw_wf& W, hipStream_t st, uint32_t builder) {
+        int r = -1;
+        (void)((feat == F && (r = wf_lists_only<F>(L, W, st, builder), true)) || ...);
+        return r;
+    }
 };
 
 // The translation units, each with its class table:
@@ -450,11 +472,15 @@ template <int TU>
 bool rtw_wf_unit_run(uint32_t feat, const rtw_launch& L, const rtw_wf& W, hipStream_t st, int n_cu, rtw_timer* T);
 template <int TU>
 uint32_t rtw_wf_unit_max_waves(int n_cu);
+template <int TU>
+int rtw_wf_unit_lists(uint32_t feat, const rtw_launch& L, const rtw_wf& W, hipStream_t st, uint32_t builder);
 #define RTW_WF_UNIT(TU)                                                                                     \
     template <>                                                                                             \
     bool rtw_wf_unit_run<TU>(uint32_t, const rtw_launch&, const rtw_wf&, hipStream_t, int, rtw_timer*);     \
     template <>                                                                                             \
-    uint32_t rtw_wf_unit_max_waves<TU>(int);
+    uint32_t rtw_wf_unit_max_waves<TU>(int);                                                                \
+    template <>                                                                                             \
+    int rtw_wf_unit_lists<TU>(uint32_t, const rtw_launch&, const rtw_wf&, hipStream_t, uint32_t);
 RTW_WF_UNIT(WF_TU_MAIN) RTW_WF_UNIT(WF_TU_SPHERES) RTW_WF_UNIT(WF_TU_LIGHTS) RTW_WF_UNIT(WF_TU_ATTRS) RTW_WF_UNIT(WF_TU_ENV)
 #undef RTW_WF_UNIT
 
@@ -467,6 +493,10 @@ template <>
 uint32_t rtw_wf_unit_max_waves<WF_TU>(int n_cu) {
     return WfUnit::max_waves(n_cu);
 }
+template <>
+int rtw_wf_unit_lists<WF_TU>(uint32_t feat, const rtw_launch& L, const rtw_wf& W, hipStream_t st, uint32_t builder) {
+    return WfUnit::lists(feat, L, W, st, builder);
+}
 
 #if !defined(RTW_WF_ENV_TU) && !defined(RTW_WF_ATTRS_TU) && !defined(RTW_WF_LIGHTS_TU) && !defined(RTW_WF_SPHERES_TU)
 template <int... TU>
@@ -475,6 +505,11 @@ struct WfUnits {
         return (rtw_wf_unit_run<TU>(feat, L, W, st, n_cu, T) || ...);
     }
     static uint32_t max_waves(int n_cu) { return std::max({rtw_wf_unit_max_waves<TU>(n_cu)...}); }
+    static bool lists(uint32_t feat, const rtw_launch& L, const rtw_wf& W, hipStream_t st, uint32_t builder) {
+        int r = -1;
+        (void)(((r = rtw_wf_unit_lists<TU>(feat, L, W, st, builder)) >= 0) || ...);
+        return r > 0;
+    }
 };
 using WfAllUnits = WfUnits<WF_TU_MAIN, WF_TU_SPHERES, WF_TU_LIGHTS, WF_TU_ATTRS, WF_TU_ENV>;
 
@@ -483,6 +518,33 @@ void rtw_wavefront_batch(const rtw_launch& L, const rtw_wf& W, void* stream, int
 }
 
 uint32_t rtw_wavefront_max_waves(int n_cu) { return WfAllUnits::max_waves(n_cu); }
+
+bool rtw_wavefront_tile_lists(const rtw_launch& L, const rtw_wf& W, void* stream, uint32_t builder) {
+    return WfAllUnits::lists(wf_pick_feat(rtw_feat_of(L)), L, W, (hipStream_t)stream, builder);
+}
+
+// Host-only test hook (include/rtw_gpu.h): tile_frustum and tile_reach -- the list builders' code, the same fp32
+// operations -- for the tile of pixels [x0, x1] x [y0, y1] and n spheres
+extern "C" int rtw_debug_tile_reach(const rtw_camera* cam, float x0, float x1, float y0, float y1, uint32_t n,
+                                    const float* centres, const float* radii, uint8_t* reach, float* tlow,
+                                    uint8_t* frame_ok) {
+    if (int rc = rtw_validate_cam(cam)) return rc;
+    if (n && (!centres || !radii || !reach || !tlow)) {
+        rtw_set_error("rtw_debug_tile_reach: null centres / radii / reach / tlow");
+        return RTW_E_INVALID;
+    }
+    rtw_launch L{};
+    rtw_launch_camera(L, cam, 0);
+    const TileFrustum F = tile_frustum(L, x0, x1, y0, y1);
+    if (frame_ok) *frame_ok = F.ok ? 1 : 0;
+    for (uint32_t i = 0; i < n; i++) {
+        float t = 0.0f;
+        reach[i] = tile_reach(F, mk(centres[3 * (size_t)i], centres[3 * (size_t)i + 1], centres[3 * (size_t)i + 2]),
+                              radii[i], t) ? 1 : 0;
+        tlow[i] = t;
+    }
+    return RTW_OK;
+}
 #endif
 
 #if defined(RTW_WF_SPHERES_TU) && defined(RTW_DIAG_WALK)

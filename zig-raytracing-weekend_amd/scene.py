@@ -766,6 +766,7 @@ class World:
         self.device = device
         self._desc = arrays.desc()
         h = C.c_void_p()
+        self._tile_lists = int(_abi.tuning(**(tuning or {})).tile_lists)
         if tuning:
             t = _abi.tuning(**tuning)
             _abi.check(L.rtw_scene_create_ex(C.byref(self._desc), device, C.byref(t), C.byref(h)), "rtw_scene_create_ex")
@@ -866,6 +867,39 @@ class World:
                                                     p(out.get("pdf")), p(out.get("sampled_dir")), p(out.get("texel"))),
                    "rtw_debug_environment")
         return out
+
+    def debug_tile_lists(self, cam, pix_begin: int = 0, pix_end: Optional[int] = None, builder: int = 0,
+                         cap: int = 0) -> tuple:
+        """rtw_debug_tile_lists: the camera-ray candidate lists a render of pixels [pix_begin, pix_end) with `cam`
+        (a Camera, initialised on demand, or an RtwCamera) would build, by builder 0 (the one a render picks), 1
+        (the flat scan) or 2 (the frustum walk) at cap 0 (the world's) or 2..128.  Returns (counts, ids, tlow,
+        centres, rr, n_tx, row0): counts (T,) uint32, 0xFFFFFFFF for a tile that walks the tree; per tile and slot
+        k < cap the leaf index ids (T, cap) uint32 (0xFFFFFFFF: never written), the bound tlow (T, cap) float32, the
+        stored centres (T, cap, 3) and squared radii rr (T, cap) float32; tile t covers x in 8 (t % n_tx) .. +7 and
+        rows row0 + 8 (t // n_tx) .. +7.  GPU worlds of static spheres only."""
+        c = cam
+        if not isinstance(cam, _abi.RtwCamera):
+            if cam.derived is None:
+                cam.init()
+            c = cam.derived
+        end = int(c.size) if pix_end is None else int(pix_end)
+        if not 0 <= pix_begin < end <= c.size:
+            raise ValueError("debug_tile_lists: empty pixel range or out of the image")
+        w = int(c.image_width)
+        tiles = ((w + 7) // 8) * (((end - 1) // w - pix_begin // w + 1 + 7) // 8)
+        width = int(cap) if cap else 128
+        counts = np.zeros(tiles, np.uint32)
+        raw = np.zeros((tiles, width, 8), np.uint32)
+        n, n_tx, row0 = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _abi.check(_abi.lib().rtw_debug_tile_lists(self.handle, C.byref(c), pix_begin, end, builder, cap, C.byref(n),
+                                                   C.byref(n_tx), C.byref(row0), counts.ctypes.data, raw.ctypes.data,
+                                                   tiles), "rtw_debug_tile_lists")
+        assert n.value == tiles
+        if not cap:  # the world's cap (rtw_tuning.tile_lists): what the call wrote is (tiles, that cap, 8), packed
+            width = min(self._tile_lists, 128) if self._tile_lists != 1 else 32 if self.stats()["n_nodes"] <= 4096 else 128
+            raw = raw.reshape(-1)[:tiles * width * 8].reshape(tiles, width, 8)
+        f = raw.view(np.float32)
+        return counts, raw[:, :, 4].copy(), f[:, :, 5].copy(), f[:, :, 0:3].copy(), f[:, :, 3].copy(), n_tx.value, row0.value
 
     def render_guides(self, cam) -> tuple:
         """rtw_render_guides: the first-hit guide buffers of the camera's frame, (albedo, normal_depth), each a
